@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: VQ-VAE training-step throughput (volumes/s, 160x224x160) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = forward + MSE loss + backward + EMA codebook update + Adam over one batch of synthetic volumes already resident
 in HBM (BASELINE.json configs[1]/[2]: baseline_vqvae no_levels=4 no_channels=256 embedding_dim=32 num_embeddings=2048,
 bf16 MFMA, batch 8 per GPU, batch-sharded data parallel with RCCL all-reduce of gradients and EMA statistics).  Rank 0 prints
-ONE JSON line.  The oracle / CPU restatement is touched only by the `cpu_baseline` leg.
+ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline; `--full` adds every other record
+(per-kernel roofline pass, inference, CPU baselines, measured peaks, fp32 mode, B = 1 latency, adversarial iteration, Performer
+legs, the end-to-end chain and the regression guard).  The oracle / CPU restatement is touched only by the `cpu_baseline` leg.
+`--dump-outputs DIR` writes what the last timed step computed (see `dump_outputs`); the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -391,6 +395,39 @@ def _pmc_source(fname=None):
     return f"null: profiles/{fname} is missing or was collected on other kernel sources (csrc digest mismatch) -- re-run the PMC passes (tools/profile_round.sh)"
 
 
+DUMP_SAMPLE = 1 << 22     # elements drawn from each large output: 16 MiB of float32, so a dump stays far below 64 MB
+
+
+def _seeded_sample(t, seed, n=DUMP_SAMPLE):
+    """The whole of `t` (flattened) if it has at most `n` elements, else the elements at `n` seeded random positions (sorted, duplicates dropped):
+    the same positions in every run of the same configuration."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), n))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, last, net, flat):
+    """--dump-outputs: what the LAST timed step computed, as the caller of the step receives it -- the loss it returns, the network outputs it was taken
+    from (a seeded sample of the reconstruction, the quantization loss) and the state the step leaves (a seeded sample of the flat trainable
+    parameters after Adam, the whole EMA codebook) -- one DIR/<name>.npy each, float32 / float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    q = net.quantizer[0].impl
+    q.wait_ema()
+    torch.cuda.synchronize()
+    arrays = {"loss": np.asarray(float(loss.detach()), dtype=np.float64),
+              "quantization_loss": last["quantization_loss"].double().cpu().numpy(),
+              "reconstruction_sample": _seeded_sample(last["reconstruction"], seed=1),
+              "parameters_sample": _seeded_sample(flat.data, seed=2),
+              "codebook": q.weight.detach().float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _respawn(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, the same command line under
     torch.distributed.run) and pass their output through; rank 0 of the children prints the JSON line."""
@@ -722,7 +759,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50, help="timed steps (SURVEY 8(d): >= 50)")
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them (SURVEY 8(d): 20)")
-    ap.add_argument("--roofline-steps", type=int, default=3, help="steps of the separate per-kernel pass behind the timed region")
+    ap.add_argument("--roofline-steps", type=int, default=3, help="steps of the separate per-kernel pass behind the timed region (--full)")
     ap.add_argument("--batch", type=int, default=8, help="volumes per GPU per step (README.md:72: batch 8/GPU)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -742,7 +779,14 @@ def main():
     ap.add_argument("--opt-in-backward", action="store_true", help="A/B: per-bucket Adam slices + re-packs behind the gradients (FusedAdam in_backward) instead of one launch each after backward")
     ap.add_argument("--share-device", action="store_true",
                     help="test aid: all ranks on cuda:0 with the gloo backend (RCCL refuses two ranks per device) -- the N > 1 code path on real kernels, not a number")
+    ap.add_argument("--full", action="store_true",
+                    help="every record besides the headline (roofline pass, inference, CPU baselines, measured peaks, fp32 mode, B = 1 latency, adversarial, "
+                         "Performer, end to end, regression guard); the --no-* switches above trim it.  Off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; seeded samples of the large arrays)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.only_performer or args.only_adversarial):
+        ap.error("--dump-outputs writes the outputs of the headline VQ-VAE step: not with --dry-run / --only-performer / --only-adversarial")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # started without a launcher: spawn one process per GPU ourselves
         sys.exit(_respawn(args))
     if args.dry_run:
@@ -790,8 +834,9 @@ def main():
     loss_fn = MSELoss()
     gen = torch.Generator(device=dev).manual_seed(4 + rank)
     x = torch.rand(args.batch, 1, *VOL, generator=gen, device=dev, dtype=torch.float32)
+    last = {}
 
-    def step():
+    def step(keep=False):
         flat.zero_grad()
         out = net(x)
         loss = loss_fn(out, x)
@@ -799,6 +844,8 @@ def main():
         scale = reducer.finish()
         opt.step(grad_scale=scale)
         sched.step()
+        if keep:      # --dump-outputs, last timed step: the network outputs the loss was taken from (references only, nothing is launched)
+            last.update(reconstruction=out["reconstruction"][0].detach(), quantization_loss=out["quantization_losses"][0].detach())
         return loss
 
     for _ in range(args.warmup):
@@ -813,8 +860,9 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     marks[0].record()
+    dump = bool(args.dump_outputs) and rank == 0
     for i in range(args.steps):
-        loss = step()
+        loss = step(keep=dump and i == args.steps - 1)
         marks[i + 1].record()
     _spin_until(marks[-1])
     torch.cuda.synchronize()
@@ -830,10 +878,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.item())
+    if dump:       # before the roofline pass below trains further
+        dump_outputs(args.dump_outputs, loss, last, net, flat)
+    last.clear()
 
     # roofline pass, AFTER the timed region: a few more steps with HIP events around every launch on the launch stream (engine.KernelTimer)
     timer = None
-    if not args.no_kernel_timer:          # (every rank runs the steps -- they contain collectives --, rank 0 carries the events)
+    if args.full and not args.no_kernel_timer:          # (every rank runs the steps -- they contain collectives --, rank 0 carries the events)
         if rank == 0:
             timer = engine.KernelTimer()
             engine.TIMER = timer
@@ -906,34 +957,35 @@ def main():
             line["roofline"] = roof
         if roof_hbm is not None:
             line["roofline_hbm"] = roof_hbm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             if not args.no_performer:
                 line["cpu_baseline_performer"] = cpu_baseline_performer()
-    # "report also inference (index_quantize + decode_samples) volumes/s"
-    net.eval()
-    with torch.no_grad():
-        for _ in range(max(1, min(3, args.warmup))):
-            rec = net.decode_samples(net.index_quantize(x))
-        torch.cuda.synchronize()
+    if args.full:
+        # "report also inference (index_quantize + decode_samples) volumes/s"
+        net.eval()
+        with torch.no_grad():
+            for _ in range(max(1, min(3, args.warmup))):
+                rec = net.decode_samples(net.index_quantize(x))
+            torch.cuda.synchronize()
+            if dist.is_initialized():
+                dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                rec = net.decode_samples(net.index_quantize(x))
+            torch.cuda.synchronize()
+            if dist.is_initialized():
+                dist.barrier()
+            dti = time.perf_counter() - t1
         if dist.is_initialized():
-            dist.barrier()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            rec = net.decode_samples(net.index_quantize(x))
-        torch.cuda.synchronize()
-        if dist.is_initialized():
-            dist.barrier()
-        dti = time.perf_counter() - t1
-    if dist.is_initialized():
-        t = torch.tensor([dti], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dti = float(t.item())
-    if rank == 0:
-        line["inference"] = {"metric": "vqvae_extract_decode_volumes_per_sec", "value": round(args.batch * world * args.steps / dti, 3), "unit": "volumes/s",
-                             "ms_per_step": round(dti / args.steps * 1e3, 3), "workload": "index_quantize + decode_samples (eval), same volumes"}
-    del rec
-    if rank == 0 and world == 1 and not args.no_extras:
+            t = torch.tensor([dti], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dti = float(t.item())
+        if rank == 0:
+            line["inference"] = {"metric": "vqvae_extract_decode_volumes_per_sec", "value": round(args.batch * world * args.steps / dti, 3), "unit": "volumes/s",
+                                 "ms_per_step": round(dti / args.steps * 1e3, 3), "workload": "index_quantize + decode_samples (eval), same volumes"}
+        del rec
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         if roof is not None:
             pk = measured_peaks(dev)
             line["roofline"]["peak_measured"] = pk
@@ -951,22 +1003,22 @@ def main():
     secondary = secondary_14k = None
     del net, flat, opt, reducer, x
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         line["latency_b1"] = bench_latency_b1(dev, dtype)
         line["adversarial"] = bench_adversarial(dev, dtype, args.batch)
-    if not args.no_performer:
+    if args.full and not args.no_performer:
         secondary = bench_performer(args, rank, world, dev)
         torch.cuda.empty_cache()
         if args.performer_shape == "10,14,10":   # BASELINE.json configs[3] says "~14k-token" latents: also the 20x28x25 grid, one sequence per GPU
             secondary_14k = bench_performer(args, rank, world, dev, shape=(20, 28, 25), batch=1)
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.no_end_to_end:
         line["end_to_end"] = bench_end_to_end()
     if rank == 0:
         if secondary is not None:
             line["secondary"] = secondary
         if secondary_14k is not None:
             line["secondary_14k"] = secondary_14k
-        if world == 1:
+        if args.full and world == 1:
             rep = regression_report(line)
             if rep is not None:
                 line["regression_guard"] = rep
