@@ -266,6 +266,23 @@ int sa_gelu(const void *u, int u_dtype, void *h, int h_dtype, int64_t n, void *s
 int sa_rezero_fwd(const float *x, const void *F, int f_dtype, const float *g, float *y, void *y_lp, int lp_dtype, int64_t n, void *stream);
 int sa_rezero_bwd(const float *dy, const void *F, int f_dtype, const float *g, void *dF, int df_dtype, float *dg, int64_t n, void *stream);
 int sa_axpy(float *y, const float *x, float alpha, int64_t n, void *stream);
+/* ==== dropout (performer_pytorch FeedForward / SelfAttention / LocalAttention nn.Dropout; reference run_transformer.py:83-84 --ff_dropout / --attn_dropout,
+ * src/networks/transformers/performer.py:95-96,212-213) ====
+ * Keep decisions are stateless: Philox4x32-10 of (seed, site, element index e), keep iff word >= min(floor(p 2^32), 2^32 - 1), kept values scaled by
+ * fp32(1 / (1 - p)); 0 <= p < 1 (SA_EINVAL otherwise).  Exact indexing: csrc/dropout.h (dense sites e = row * cols + col of a contiguous tensor).
+ * sa_dropout_mask: out[e] = keep(e) ? (scaled ? 1 / (1 - p) : 1) : 0 for e < n (replays a site's mask).
+ * sa_dropout_apply: x (SA_F32 | SA_BF16) *= keep / (1 - p) in place (FeedForward: the GELU output h before w2).
+ * sa_dropout_gelu_bwd: du = dh * keep / (1 - p) * gelu'(u)  (dtypes f32/f32/f32, bf16/bf16/bf16, bf16/f32/bf16, f32/f32/bf16).
+ * sa_dropout_rezero_fwd: F' = F * keep / (1 - p) written back to F, y = x + g F', optional y_lp copy (SelfAttention output -> ReZero gate or pre-LayerNorm
+ *   residual with g = 1).  sa_dropout_rezero_bwd: dF = g dy keep / (1 - p), dg += sum dy F' (F = the forward's F'). */
+int sa_dropout_mask(float *out, int64_t n, float p, uint64_t seed, uint32_t site, int scaled, void *stream);
+int sa_dropout_apply(void *x, int dtype, int64_t n, float p, uint64_t seed, uint32_t site, void *stream);
+int sa_dropout_gelu_bwd(const void *dh, int dh_dtype, const void *u, int u_dtype, void *du, int du_dtype, int64_t n, float p, uint64_t seed, uint32_t site,
+                        void *stream);
+int sa_dropout_rezero_fwd(const float *x, void *F, int f_dtype, const float *g, float *y, void *y_lp, int lp_dtype, int64_t n, float p, uint64_t seed,
+                          uint32_t site, void *stream);
+int sa_dropout_rezero_bwd(const float *dy, const void *F, int f_dtype, const float *g, void *dF, int df_dtype, float *dg, int64_t n, float p, uint64_t seed,
+                          uint32_t site, void *stream);
 /* FAVOR+ softmax_kernel feature map on top of the projection GEMM output dd [rows, LDF] (rows = B*N*G):
  * feat = m^-1/2 (exp(dd - |x|^2 d^-1/2 / 2 - stab) + 1e-4), stab = row max (is_query = 1) or the GLOBAL max (keys; gmax_ws = 8 bytes:
  * is_query = 0 computes it here, is_query = 2 takes it as left there by sa_favor_project). */
@@ -357,6 +374,15 @@ int sa_local_attn_fwd(const float *q, int q_stride, int q_off, const float *k, i
 int sa_local_attn_bwd(const float *q, int q_stride, int q_off, const float *k, int k_stride, int k_off, const float *v, int v_stride, int v_off,
                       const float *out, const float *dout, int o_stride, int o_off, const float *lse, float *dq, float *dk, float *dv,
                       float *Dbuf, int B, int N, int L, int W, int dh, void *dv_lp, void *stream);
+/* the same with dropout on the window probabilities (LocalAttention(dropout=attn_dropout) of performer_pytorch 1.0.11: dropout(softmax(dots)) @ v), both
+ * arithmetic paths; element index of P[b, h, i, j]: e = ((b * L + h) * N + i) * N + j.  lse is the UNDROPPED softmax's, o = (P Z / (1 - p)) v; backward
+ * dS = P (Z dP / (1 - p) - D) with D = rowsum(dout * out) of the dropped out, dv from the dropped P. */
+int sa_local_attn_fwd_dropout(const float *q, int q_stride, int q_off, const float *k, int k_stride, int k_off, const float *v, int v_stride, int v_off,
+                              float *o, int o_stride, int o_off, float *lse, int B, int N, int L, int W, int dh, void *o_lp, float p, uint64_t seed,
+                              uint32_t site, void *stream);
+int sa_local_attn_bwd_dropout(const float *q, int q_stride, int q_off, const float *k, int k_stride, int k_off, const float *v, int v_stride, int v_off,
+                              const float *out, const float *dout, int o_stride, int o_off, const float *lse, float *dq, float *dk, float *dv,
+                              float *Dbuf, int B, int N, int L, int W, int dh, void *dv_lp, float p, uint64_t seed, uint32_t site, void *stream);
 /* CELoss (losses/transformer/transformer.py:24-33): loss_sum += sum_r (lse_r - logit[r,target_r]); dlogits = (softmax - onehot) * gscale */
 int sa_cross_entropy(const float *logits, const int64_t *target, int64_t R, int V, float *loss_sum, void *dlogits, int d_dtype, float gscale,
                      void *stream);

@@ -117,6 +117,11 @@ _SIGS = {
     "sa_rezero_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "sa_rezero_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "sa_axpy": (c_int, [c_void_p, c_void_p, c_float, c_int64, c_void_p]),
+    "sa_dropout_mask": (c_int, [c_void_p, c_int64, c_float, ctypes.c_uint64, ctypes.c_uint32, c_int, c_void_p]),
+    "sa_dropout_apply": (c_int, [c_void_p, c_int, c_int64, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "sa_dropout_gelu_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "sa_dropout_rezero_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "sa_dropout_rezero_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
     "sa_favor_features_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "sa_favor_features_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int64, c_int, c_int, c_void_p]),
@@ -154,6 +159,11 @@ _SIGS = {
                                   c_int, c_int, c_void_p, c_void_p]),
     "sa_local_attn_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sa_local_attn_fwd_dropout": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                          c_int, c_int, c_int, c_void_p, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "sa_local_attn_bwd_dropout": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, ctypes.c_uint64,
+                                          ctypes.c_uint32, c_void_p]),
     "sa_bn_forward": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_float, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p]),
     "sa_bn_backward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -50,9 +50,9 @@ __device__ __forceinline__ bool la_allowed(int i, int j, int W, int N) {
 }
 
 
-// MODE 0: forward (o, lse)   MODE 1: backward wrt q (dq, D)
-template <int MODE>
-__global__ __launch_bounds__(256) void local_attn_q_kernel(const LAArgs a) {
+// MODE 0: forward (o, lse)   MODE 1: backward wrt q (dq, D);  DROP: dropout on the probabilities (see local_attn_q_split_body)
+template <int MODE, bool DROP>
+__device__ __forceinline__ void local_attn_q_exact(const LAArgs& a, const DropParams& dp_) {
     __shared__ __attribute__((aligned(16))) float sK[LT * LLD], sV[LT * LLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qi = lane & 15, g = lane >> 4;
@@ -63,6 +63,7 @@ __global__ __launch_bounds__(256) void local_attn_q_kernel(const LAArgs a) {
     const bool vq = iq < a.N;
     const int64_t rb = (int64_t)b * a.N;
     const int qoff = a.q_off + h * 64, koff = a.k_off + h * 64, voff = a.v_off + h * 64, ooff = a.o_off + h * 64;
+    const uint64_t erow = DROP ? (((uint64_t)b * a.L + h) * a.N + iq) * a.N : 0;   // dropout element index of (b, h, iq, key 0)
 
     float Qreg[16], Greg[16];  // B operands: scaled q (and dO in backward) of this lane's query, d = dd*4 + g
     float lse = 0.f, Dv = 0.f;
@@ -133,14 +134,26 @@ __global__ __launch_bounds__(256) void local_attn_q_kernel(const LAArgs a) {
             m_run = m_new;
 #pragma unroll
             for (int df = 0; df < 4; ++df) acc[df] *= alpha;
+            if (DROP) {
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    float z[4];
+                    drop_factors4(dp_, erow + (uint64_t)(kt * LT + f * 16 + g * 4), z);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) p[f][r] *= z[r];
+                }
+            }
         } else {
 #pragma unroll
-            for (int f = 0; f < 4; ++f)
+            for (int f = 0; f < 4; ++f) {
+                float z[4] = {1.f, 1.f, 1.f, 1.f};
+                if (DROP) drop_factors4(dp_, erow + (uint64_t)(kt * LT + f * 16 + g * 4), z);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float pv = la_allowed(iq, kt * LT + f * 16 + g * 4 + r, a.W, a.N) ? __expf(s[f][r] - lse) : 0.f;
-                    p[f][r] = pv * (dp[f][r] - Dv);  // dS
+                    p[f][r] = pv * (DROP ? z[r] * dp[f][r] - Dv : dp[f][r] - Dv);  // dS
                 }
+            }
         }
         const float* sR = MODE == 0 ? sV : sK;  // forward: O^T += V^T P^T ; backward: dQ^T += K^T dS^T
 #pragma unroll
@@ -170,7 +183,8 @@ __global__ __launch_bounds__(256) void local_attn_q_kernel(const LAArgs a) {
 }
 
 // dk / dv: block = 64 keys of one (batch, head); wave = 16 keys (K, V rows in registers as MFMA B operands)
-__global__ __launch_bounds__(256) void local_attn_kv_kernel(const LAArgs a) {
+template <bool DROP>
+__device__ __forceinline__ void local_attn_kv_exact(const LAArgs& a, const DropParams& dp_) {
     __shared__ __attribute__((aligned(16))) float sQ[LT * LLD], sG[LT * LLD];
     __shared__ float sLse[LT], sD[LT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -224,8 +238,9 @@ __global__ __launch_bounds__(256) void local_attn_kv_kernel(const LAArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int il = f * 16 + g * 4 + r;
                 const float pv = la_allowed(qt * LT + il, kj, a.W, a.N) ? __expf(s[f][r] - sLse[il]) : 0.f;
-                p[f][r] = pv;
-                ds[f][r] = pv * (dp[f][r] - sD[il]);
+                const float z = DROP ? drop_factor(dp_, (((uint64_t)b * a.L + h) * a.N + (uint64_t)(qt * LT + il)) * a.N + kj) : 1.f;
+                p[f][r] = DROP ? pv * z : pv;
+                ds[f][r] = pv * (DROP ? z * dp[f][r] - sD[il] : dp[f][r] - sD[il]);
             }
 #pragma unroll
         for (int df = 0; df < 4; ++df)
@@ -248,6 +263,13 @@ __global__ __launch_bounds__(256) void local_attn_kv_kernel(const LAArgs a) {
 }
 
 template <int MODE>
+__global__ __launch_bounds__(256) void local_attn_q_kernel(const LAArgs a) { local_attn_q_exact<MODE, false>(a, DropParams{}); }
+__global__ __launch_bounds__(256) void local_attn_kv_kernel(const LAArgs a) { local_attn_kv_exact<false>(a, DropParams{}); }
+template <int MODE>
+__global__ __launch_bounds__(256) void local_attn_q_drop_kernel(const LAArgs a, const DropParams d) { local_attn_q_exact<MODE, true>(a, d); }
+__global__ __launch_bounds__(256) void local_attn_kv_drop_kernel(const LAArgs a, const DropParams d) { local_attn_kv_exact<true>(a, d); }
+
+template <int MODE>
 __global__ __launch_bounds__(256, MODE == 0 ? 3 : 2) void local_attn_q_split_kernel(const LAArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[LA_SPLIT_LDS];
     local_attn_q_split_body<MODE>(a, (int)blockIdx.x, lds);
@@ -255,6 +277,16 @@ __global__ __launch_bounds__(256, MODE == 0 ? 3 : 2) void local_attn_q_split_ker
 __global__ __launch_bounds__(256) void local_attn_kv_split_kernel(const LAArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[LA_SPLIT_LDS];
     local_attn_kv_split_body(a, (int)blockIdx.x, lds);
+}
+// the dropout variants (sa_local_attn_fwd_dropout / _bwd_dropout)
+template <int MODE>
+__global__ __launch_bounds__(256, MODE == 0 ? 3 : 2) void local_attn_q_split_drop_kernel(const LAArgs a, const DropParams d) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LA_SPLIT_LDS];
+    local_attn_q_split_body<MODE, true>(a, (int)blockIdx.x, lds, d);
+}
+__global__ __launch_bounds__(256) void local_attn_kv_split_drop_kernel(const LAArgs a, const DropParams d) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LA_SPLIT_LDS];
+    local_attn_kv_split_body<true>(a, (int)blockIdx.x, lds, d);
 }
 
 }  // namespace sa
@@ -290,6 +322,43 @@ extern "C" int sa_local_attn_bwd(const float* q, int q_stride, int q_off, const 
     SA_CHECK_LAUNCH();
     if (exact) SA_LAUNCH(local_attn_kv_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a);
     else SA_LAUNCH(local_attn_kv_split_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sa_local_attn_fwd_dropout(const float* q, int q_stride, int q_off, const float* k, int k_stride, int k_off, const float* v, int v_stride,
+                                         int v_off, float* o, int o_stride, int o_off, float* lse, int B, int N, int L, int W, int dh, void* o_lp, float p,
+                                         uint64_t seed, uint32_t site, void* stream) {
+    if (!q || !k || !v || !o || !lse || !(p >= 0.f && p < 1.f)) return SA_EINVAL;
+    LAArgs a = {};
+    const int rc = fill_la(a, q_stride, q_off, k_stride, k_off, v_stride, v_off, o_stride, o_off, B, N, L, W, dh);
+    if (rc) return rc;
+    a.q = q; a.k = k; a.v = v; a.o = o; a.lse_out = lse; a.o_lp = (unsigned short*)o_lp;
+    const DropParams d = make_drop(p, seed, site);
+    const unsigned nblk = (unsigned)(B * L * ((N + LT - 1) / LT));
+    if (la_exact()) SA_LAUNCH(local_attn_q_drop_kernel<0>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, d);
+    else SA_LAUNCH(local_attn_q_split_drop_kernel<0>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, d);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sa_local_attn_bwd_dropout(const float* q, int q_stride, int q_off, const float* k, int k_stride, int k_off, const float* v, int v_stride,
+                                         int v_off, const float* out, const float* dout, int o_stride, int o_off, const float* lse, float* dq, float* dk,
+                                         float* dv, float* Dbuf, int B, int N, int L, int W, int dh, void* dv_lp, float p, uint64_t seed, uint32_t site,
+                                         void* stream) {
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !Dbuf || !(p >= 0.f && p < 1.f)) return SA_EINVAL;
+    LAArgs a = {};
+    const int rc = fill_la(a, q_stride, q_off, k_stride, k_off, v_stride, v_off, o_stride, o_off, B, N, L, W, dh);
+    if (rc) return rc;
+    a.q = q; a.k = k; a.v = v; a.out = out; a.dout = dout; a.lse_in = lse; a.dq = dq; a.dk = dk; a.dv = dv; a.Dbuf_out = Dbuf; a.Dbuf_in = Dbuf; a.dv_lp = (unsigned short*)dv_lp;
+    const DropParams d = make_drop(p, seed, site);
+    const unsigned nblk = (unsigned)(B * L * ((N + LT - 1) / LT));
+    const bool exact = la_exact();
+    if (exact) SA_LAUNCH(local_attn_q_drop_kernel<1>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, d);
+    else SA_LAUNCH(local_attn_q_split_drop_kernel<1>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, d);
+    SA_CHECK_LAUNCH();
+    if (exact) SA_LAUNCH(local_attn_kv_drop_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, d);
+    else SA_LAUNCH(local_attn_kv_split_drop_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, d);
     SA_CHECK_LAUNCH();
     return 0;
 }

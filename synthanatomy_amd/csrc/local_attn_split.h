@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "dropout.h"
 #include "sa_common.h"
 #include "split_bf16.h"
 
@@ -112,9 +113,11 @@ __device__ __forceinline__ void la_block(const LAArgs& a, const uint16_t* order,
 }
 
 // MODE 0: forward (o, lse)   MODE 1: backward wrt q (dq, D)
+// DROP (sa_local_attn_*_dropout): FlashAttention-style dropout on the probabilities with the keep factors Z / (1 - p) of csrc/dropout.h -- lse stays the undropped
+// softmax, O = (P o Z/(1-p)) V, dS = P o (Z/(1-p) o dP - D) with D = rowsum(dO o O) of the dropped O.  DROP = false is the kernel without dropout.
 constexpr int LA_SPLIT_LDS = 4 * LTB + 512;   // bytes of LDS either body needs
-template <int MODE>
-__device__ __forceinline__ void local_attn_q_split_body(const LAArgs& a, const int bid, unsigned char* const lds) {
+template <int MODE, bool DROP = false>
+__device__ __forceinline__ void local_attn_q_split_body(const LAArgs& a, const int bid, unsigned char* const lds, const DropParams& dp_ = DropParams{}) {
     unsigned char* const sKh = lds, * const sKl = lds + LTB, * const sVh = lds + 2 * LTB, * const sVl = lds + 3 * LTB;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = lane & 15, g = lane >> 4;
@@ -127,6 +130,7 @@ __device__ __forceinline__ void local_attn_q_split_body(const LAArgs& a, const i
     const int64_t rb = (int64_t)b * a.N;
     const int qoff = a.q_off + h * 64, koff = a.k_off + h * 64, voff = a.v_off + h * 64, ooff = a.o_off + h * 64;
     const int64_t qrow = rb + min(iq, a.N - 1);
+    const uint64_t erow = DROP ? (((uint64_t)b * a.L + h) * a.N + iq) * a.N : 0;   // dropout element index of (b, h, iq, key 0)
 
     const int kt_lo = max(0, (q0 / a.W - 1) * a.W) / LT;
     const int kt_hi = min(a.N - 1, q0 + LT - 1) / LT;
@@ -216,11 +220,23 @@ __device__ __forceinline__ void local_attn_q_split_body(const LAArgs& a, const i
             m_run = m_new;
 #pragma unroll
             for (int df = 0; df < 4; ++df) acc[df] *= alpha;
+            if (DROP) {   // the P V operand: P o Z / (1 - p) (l_run above summed the undropped P)
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    float z[4];
+                    drop_factors4(dp_, erow + (uint64_t)(jb + f * 16), z);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) p[f][r] *= z[r];
+                }
+            }
         } else {
 #pragma unroll
-            for (int f = 0; f < 4; ++f)
+            for (int f = 0; f < 4; ++f) {
+                float z[4] = {1.f, 1.f, 1.f, 1.f};
+                if (DROP) drop_factors4(dp_, erow + (uint64_t)(jb + f * 16), z);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) p[f][r] = __expf(s[f][r] - lse) * (dp[f][r] - Dv);  // dS
+                for (int r = 0; r < 4; ++r) p[f][r] = __expf(s[f][r] - lse) * (DROP ? z[r] * dp[f][r] - Dv : dp[f][r] - Dv);  // dS
+            }
         }
         short8_t Ph[2], Pl[2];
         acc_to_operand(Ph, Pl, p);
@@ -246,7 +262,8 @@ __device__ __forceinline__ void local_attn_q_split_body(const LAArgs& a, const i
 }
 
 // dk / dv: block = 64 keys of one (batch, head); wave = 16 keys whose K, V rows are the register-resident B operands
-__device__ __forceinline__ void local_attn_kv_split_body(const LAArgs& a, const int bid, unsigned char* const lds) {
+template <bool DROP = false>
+__device__ __forceinline__ void local_attn_kv_split_body(const LAArgs& a, const int bid, unsigned char* const lds, const DropParams& dp_ = DropParams{}) {
     unsigned char* const sQh = lds, * const sQl = lds + LTB, * const sGh = lds + 2 * LTB, * const sGl = lds + 3 * LTB;
     float* const sLse = (float*)(lds + 4 * LTB), * const sD = sLse + LT;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -332,7 +349,13 @@ __device__ __forceinline__ void local_attn_kv_split_body(const LAArgs& a, const 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 p[f][r] = __expf(s[f][r] - lv[r]);
-                ds[f][r] = p[f][r] * (dp[f][r] - dv4[r]);
+                if (DROP) {   // dV uses the dropped P, dS = P (Z dP / (1 - p) - D)
+                    const float z = drop_factor(dp_, (((uint64_t)b * a.L + h) * a.N + (uint64_t)(qt * LT + f * 16 + g * 4 + r)) * a.N + kj);
+                    ds[f][r] = p[f][r] * (z * dp[f][r] - dv4[r]);
+                    p[f][r] *= z;
+                } else {
+                    ds[f][r] = p[f][r] * (dp[f][r] - dv4[r]);
+                }
             }
         }
         short8_t Ph[2], Pl[2];

@@ -238,8 +238,14 @@ class BasePerformer(nn.Module):
         unsupported = dict(reversible=reversible, generalized_attention=generalized_attention, use_scalenorm=use_scalenorm, ff_glu=ff_glu,
                            cross_attend=cross_attend, no_projection=no_projection)
         bad = [k for k, v in unsupported.items() if v]
-        if bad or not causal or ff_dropout or attn_dropout or ff_chunks != 1:
+        if bad or not causal or ff_chunks != 1:
             raise NotImplementedError(f"performer on MI355X implements the causal ReZero / pre-LayerNorm FAVOR+ configuration; unsupported: {bad}")
+        for name, p in (("ff_dropout", ff_dropout), ("attn_dropout", attn_dropout)):
+            if not 0.0 <= float(p) < 1.0:
+                raise ValueError(f"{name} must lie in [0, 1) (nn.Dropout's keep probability 1 - p must be positive), got {p}")
+        # nn.Dropout(ff_dropout) on the FF hidden, nn.Dropout(attn_dropout) on the attention output and on the local heads' window probabilities
+        # (performer_pytorch 1.0.11 FeedForward / SelfAttention / LocalAttention); counter-based masks, csrc/dropout.h
+        self.ff_dropout, self.attn_dropout = float(ff_dropout), float(attn_dropout)
         if isinstance(local_attn_heads, int):
             local_attn_heads = (local_attn_heads,)
         local_attn_heads = tuple(local_attn_heads) * depth if len(local_attn_heads) == 1 else tuple(local_attn_heads)
@@ -400,8 +406,10 @@ class _GradCtx:
 class _LayerEngine:
     """Hand-scheduled forward / backward of ONE (attention, feed-forward) block."""
 
-    def __init__(self, attn_wrap, ff_wrap, dim, dtype, use_rezero):
+    def __init__(self, attn_wrap, ff_wrap, dim, dtype, use_rezero, index=0, ff_dropout=0.0, attn_dropout=0.0):
         self.aw, self.fw, self.dim, self.dtype, self.rezero = attn_wrap, ff_wrap, dim, dtype, use_rezero
+        # dropout sites of this layer (csrc/dropout.h): 4 * index + 0 FF hidden, + 1 attention output, + 2 local-window probabilities
+        self.p_ff, self.p_attn, self.site = ff_dropout, attn_dropout, 4 * index
         sa: SelfAttention = attn_wrap.fn
         ff: FeedForward = ff_wrap.fn.fn
         self.sa, self.ff = sa, ff
@@ -540,11 +548,13 @@ class _LayerEngine:
         return y, stats
 
     # ---------------------------------------------------------------------------------------------- forward
-    def fwd(self, x, B, N, tape, x_lp=None):
+    def fwd(self, x, B, N, tape, x_lp=None, seed=None):
         """x_lp: the compute-dtype copy of x when the producer already wrote one (the previous block's ReZero kernel); the copy of this block's
-        output is left in ``self.out_lp`` for the next block (saves two cast launches per block on the ReZero path)."""
+        output is left in ``self.out_lp`` for the next block (saves two cast launches per block on the ReZero path).  seed: the training forward's
+        dropout seed (None: no dropout -- eval(), or p = 0)."""
         self._sync()
         lib, st, dev, T = _ffi.lib(), _ffi.stream(), x.device, self.dtype
+        pf, pa = (self.p_ff, self.p_attn) if seed is not None else (0.0, 0.0)
         R, H, G, L, dh, m, LDF = B * N, self.H, self.G, self.L, self.dh, self.m, self.LDF
         inner = H * dh
         f32 = torch.float32
@@ -564,10 +574,11 @@ class _LayerEngine:
         # throughput mode: the attention kernels write the bf16 operand of to_out next to the fp32 rows (no cast launch); needs every head on a kernel that can
         attn_lp = (torch.empty(R, inner, dtype=T, device=dev)
                    if (T == torch.bfloat16 and (G == 0 or self._fused_favor()) and not debug.host("no_lp_mirrors")) else None)
-        sv = dict(x=x, xa=xa, xaT=xaT, st_a=st_a, q=q, k=k, v=v, attn=attn)
+        sv = dict(x=x, xa=xa, xaT=xaT, st_a=st_a, q=q, k=k, v=v, attn=attn, seed=seed)
         # throughput mode with both kinds of heads: the local-window heads' blocks ride in the FAVOR+ launches (sa_local_attn_args): rotary first, no launch of their own
+        # (not with attn_dropout: the co-launched bodies carry no dropout, the local heads run the sa_local_attn_fwd_dropout launch below)
         la_args = None
-        if G > 0 and L > 0 and self._fused_favor() and not debug.host("no_attn_colaunch"):
+        if G > 0 and L > 0 and self._fused_favor() and not debug.host("no_attn_colaunch") and not pa:
             la_args = self._local_fwd_prep(q, k, v, qs, attn, attn_lp, B, N, R, dev, sv)
         if G > 0 and self._fused_favor():
             tiles, ps = self._proj_tiles()
@@ -639,7 +650,11 @@ class _LayerEngine:
             sv.update(qg=qg, kg=kg, ddq=ddq, ddk=ddk, qf=qf, kf=kf, gws=gws, Z=Z, inv=inv, scan_state=ws if (Z is None and tape is not None) else None)
         if L > 0 and "lse" not in sv:          # (not prepared for the co-launch)
             self._local_fwd_prep(q, k, v, qs, attn, attn_lp, B, N, R, dev, sv)
-        if L > 0 and la_args is None:
+        if L > 0 and la_args is None and pa:
+            qr, kr, lse = sv["qr"], sv["kr"], sv["lse"]
+            _ck(lib.sa_local_attn_fwd_dropout(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh,
+                                              _ffi.ptr(lse), B, N, L, self.W, dh, _ffi.ptr(attn_lp), pa, seed, self.site + 2, st), "sa_local_attn_fwd_dropout")
+        elif L > 0 and la_args is None:
             qr, kr, lse = sv["qr"], sv["kr"], sv["lse"]
             _ck(lib.sa_local_attn_fwd(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh, _ffi.ptr(lse),
                                       B, N, L, self.W, dh, _ffi.ptr(attn_lp), st), "sa_local_attn_fwd")
@@ -647,7 +662,14 @@ class _LayerEngine:
         ga = self._gate(self.aw, dev)
         gf = self._gate(self.fw, dev)
         fuse_epi = lp and not debug.host("no_fused_epilogues")
-        if fuse_epi:
+        if pa:
+            # attn_dropout: F' = dropout(to_out(attn)) and x1 = x + g F' (+ its bf16 copy) in one launch after the plain to_out GEMM; F' is what the gate gradient reads
+            Fa = self.ops["to_out"].fprop(_as5(attnT)).view(R, self.dim)
+            x1 = torch.empty_like(x)
+            x1T = torch.empty(x.shape, dtype=T, device=dev) if lp else None
+            _ck(lib.sa_dropout_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), _ffi.ptr(x1T), _ffi.dtype_id(T) if lp else 0,
+                                          x.numel(), pa, seed, self.site + 1, st), "sa_dropout_rezero_fwd")
+        elif fuse_epi:
             # throughput mode: x1 = x + g F leaves the to_out launch itself (fp32 residual stream + its bf16 copy for the next dense layer + the branch
             # output F the ReZero backward needs) -- no sa_rezero_fwd launch, F is never re-read
             x1, Fa, x1T = self.ops["to_out"].fprop(_as5(attnT), out_dtype=f32, alpha=ga, addend=_as5(x), want_pre=True, want_lp=True)
@@ -664,12 +686,16 @@ class _LayerEngine:
             # h = gelu(u) and the pre-activation u (for the GELU backward) from ONE launch; x2 = x1 + g F from the w2 launch
             h, u, _ = self.ops["w1"].fprop(_as5(xfT), act=_ffi.ACT_GELU, want_pre=True)
             h, u = h.view(R, -1), u.view(R, -1)
+            if pf:   # ff_dropout: h *= keep / (1 - p) in place, between the GELU and w2 (u stays the undropped pre-activation)
+                _ck(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
             x2, Ff, x2T = self.ops["w2"].fprop(_as5(h), out_dtype=f32, alpha=gf, addend=_as5(x1), want_pre=True, want_lp=True)
             x2, Ff, x2T = x2.view(R, self.dim), Ff.view(R, self.dim), x2T.view(R, self.dim)
         else:
             u = self.ops["w1"].fprop(_as5(xfT)).view(R, -1)
             h = torch.empty_like(u)
             _ck(lib.sa_gelu(_ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(h), _ffi.dtype_id(h.dtype), u.numel(), st), "sa_gelu")
+            if pf:
+                _ck(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
             Ff = self.ops["w2"].fprop(_as5(h)).view(R, self.dim)
             x2 = torch.empty_like(x)
             x2T = torch.empty(x.shape, dtype=T, device=dev) if lp else None
@@ -802,12 +828,24 @@ class _LayerEngine:
         return x2
 
     # ---------------------------------------------------------------------------------------------- backward
-    def _post_bwd(self, wrap, dy, Fout, gc, dev):
-        """through y = x + g * F: returns dF (compute dtype) and accumulates dg"""
+    def _post_bwd(self, wrap, dy, Fout, gc, dev, drop=None):
+        """through y = x + g * F: returns dF (compute dtype) and accumulates dg.  drop = (p, seed, site): F = dropout(branch), Fout the dropped F' of the
+        forward -- dF = g dy keep / (1 - p)"""
         lib, st = _ffi.lib(), _ffi.stream()
         dF = torch.empty(dy.shape, dtype=self.dtype, device=dev)
         g = self._gate(wrap, dev)
         dg = gc.buf(wrap.g) if self.rezero else torch.zeros((), device=dev)
+        if drop is not None:
+            p, seed, site = drop
+            det = self.rezero and debug.deterministic()
+            scratch = torch.zeros(1 + 1024, dtype=torch.float32, device=dev) if det else None
+            _ck(lib.sa_dropout_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype),
+                                          _ffi.ptr(scratch if det else dg), dy.numel(), p, seed, site, st), "sa_dropout_rezero_bwd")
+            if det:    # d g = <dy, F'> in a fixed order, as below
+                _ck(lib.sa_dot_det(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), dy.numel(), _ffi.ptr(dg), 1, _ffi.ptr(scratch[1:]), st), "sa_dot_det")
+            if self.rezero:
+                gc.done(wrap.g)
+            return dF
         if self.rezero and debug.deterministic():
             # --deterministic: d g = <dy, F> in a fixed order (sa_dot_det) instead of one atomic per block; the elementwise half of the kernel runs as usual
             scratch = torch.zeros(1 + 1024, dtype=torch.float32, device=dev)
@@ -852,11 +890,22 @@ class _LayerEngine:
         f32 = torch.float32
         ops, sa, ff = self.ops, self.sa, self.ff
         r5 = (1, 1, R)
+        seed = sv.get("seed")
+        pf, pa = (self.p_ff, self.p_attn) if seed is not None else (0.0, 0.0)
         # ---- feed-forward block
         dFf = self._post_bwd(self.fw, dx2, sv["Ff"], gc, dev)
         gc.wgrad(ops["w2"], _as5(sv["h"]), _as5(dFf), gc.buf(ff.w2.weight), gc.buf(ff.w2.bias))
         gc.done(ff.w2.weight, ff.w2.bias)
-        du = ops["w2"].dgrad(_as5(dFf), r5, mask=_as5(sv["u"]), mask_mode=MASK_GELU)
+        if pf:   # ff_dropout: du = dh keep / (1 - p) gelu'(u) replaces the MASK_GELU epilogue
+            dh_ = ops["w2"].dgrad(_as5(dFf), r5)
+            u = sv["u"]
+            assert dh_.shape[-1] == u.shape[-1] and dh_.numel() == u.numel()
+            du = torch.empty_like(dh_)
+            _ck(lib.sa_dropout_gelu_bwd(_ffi.ptr(dh_), _ffi.dtype_id(dh_.dtype), _ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(du), _ffi.dtype_id(du.dtype), u.numel(),
+                                        pf, seed, self.site, st), "sa_dropout_gelu_bwd")
+            del dh_
+        else:
+            du = ops["w2"].dgrad(_as5(dFf), r5, mask=_as5(sv["u"]), mask_mode=MASK_GELU)
         gc.wgrad(ops["w1"], _as5(sv["xfT"]), du, gc.buf(ff.w1.weight), gc.buf(ff.w1.bias))
         gc.done(ff.w1.weight, ff.w1.bias)
         if self.rezero:
@@ -865,7 +914,7 @@ class _LayerEngine:
             dxf = ops["w1"].dgrad(du, r5, out_dtype=f32).view(R, self.dim)
             dx1 = self._pre_bwd(self.fw, dxf, dx2, sv["x1"], sv["st_f"], R, gc)
         # ---- attention block
-        dFa = self._post_bwd(self.aw, dx1, sv["Fa"], gc, dev)
+        dFa = self._post_bwd(self.aw, dx1, sv["Fa"], gc, dev, drop=(pa, seed, self.site + 1) if pa else None)
         gc.wgrad(ops["to_out"], _as5(sv["attnT"]), _as5(dFa), gc.buf(sa.to_out.weight), gc.buf(sa.to_out.bias))
         gc.done(sa.to_out.weight, sa.to_out.bias)
         dattn = ops["to_out"].dgrad(_as5(dFa), r5, out_dtype=f32).view(R, inner)
@@ -895,7 +944,7 @@ class _LayerEngine:
             dden = torch.empty(R * G, dtype=f32, device=dev)
             tsum = torch.empty(B * G * ((N + 63) // 64), dtype=f32, device=dev)
             la_args = None
-            if L > 0 and sv.get("scan_state") is not None and not debug.host("no_attn_colaunch"):
+            if L > 0 and sv.get("scan_state") is not None and not debug.host("no_attn_colaunch") and not pa:
                 # the local-window heads' backward blocks ride in the FAVOR+ launches (as in the forward pass); dq / dk of the local heads come out in ROTATED
                 # space (dqkr) and are rotated back below
                 dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
@@ -977,7 +1026,13 @@ class _LayerEngine:
                                                       _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(k)")
         if L > 0:
             cosb, sinb = self._rot_tables(N, dev)
-            if not local_done:
+            if not local_done and pa:
+                dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
+                Db = torch.empty(R * L, dtype=f32, device=dev)
+                _ck(lib.sa_local_attn_bwd_dropout(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
+                                                  inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W,
+                                                  dh, _ffi.ptr(dv_lp), pa, seed, self.site + 2, st), "sa_local_attn_bwd_dropout")
+            elif not local_done:
                 dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
                 Db = torch.empty(R * L, dtype=f32, device=dev)
                 _ck(lib.sa_local_attn_bwd(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
@@ -1021,8 +1076,9 @@ class _LayerEngine:
 class _StackChain:
     def __init__(self, base: BasePerformer, dim, dtype):
         self.base, self.dtype = base, dtype
-        self.layers = [_LayerEngine(l[0], l[1], dim, dtype, base.use_rezero) for l in base.net.layers]
+        self.layers = [_LayerEngine(l[0], l[1], dim, dtype, base.use_rezero, i, base.ff_dropout, base.attn_dropout) for i, l in enumerate(base.net.layers)]
         self.grad_sink = None
+        self.seed = None           # dropout seed of the current training forward (Performer.forward sets it; None = no dropout)
 
     def params(self):
         return [p for p in self.base.parameters()]
@@ -1037,7 +1093,7 @@ class _StackChain:
         tape = [] if record else None
         x_lp = None
         for l in self.layers:
-            x = l.fwd(x, B, N, tape, x_lp)
+            x = l.fwd(x, B, N, tape, x_lp, self.seed)
             x_lp = l.out_lp
         return x.view(B, N, D), tape
 
@@ -1276,6 +1332,7 @@ class Performer(TransformerBase):
                 l.layer_pos = self.layer_pos_emb
         self._out_op = _lin(self._out_mod(), compute_dtype)
         self._idx_cache = {}
+        self.last_dropout_seed = None      # the seed of the last training forward with ff_dropout / attn_dropout (tests replay its masks)
 
     def _out_mod(self):
         """the vocabulary projection as a (weight, bias) holder: ``to_out``, or the token table itself when the embeddings are tied"""
@@ -1534,6 +1591,12 @@ class Performer(TransformerBase):
             h = h * keep
         if self.performer.auto_check_redraw:
             self.performer.proj_updater.redraw_projections()
+        self._chain.seed = None
+        if self.training and (self.performer.ff_dropout > 0.0 or self.performer.attn_dropout > 0.0):
+            # ff_dropout / attn_dropout: ONE 64-bit seed per training forward from torch's default CPU generator (torch.manual_seed governs it as it governs
+            # nn.Dropout; no device synchronisation); every site's mask is a function of (seed, 4 * layer + site, element) -- csrc/dropout.h
+            lo, hi = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
+            self._chain.seed = self.last_dropout_seed = lo | (hi << 32)
         params = self._chain.params()
         record = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in params))
         h = _StackFn.apply(self._chain, record, h, *params)
