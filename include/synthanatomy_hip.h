@@ -202,6 +202,15 @@ int sa_subpixel_pool_fwd(const float *c, float *out, int N, int D, int H, int W,
 int sa_subpixel_pool_bwd(const float *g, void *dc, int dc_dtype, int N, int D, int H, int W, void *stream);
 /* MSELoss (losses/vqvae/vqvae.py:14-71): loss_sum[0] += sum (a-b)^2 ; grad = (a-b) * (2*gscale/n) if grad != NULL */
 int sa_mse(const float *a, const float *b, int64_t n, float *loss_sum, float *grad, float gscale, void *stream);
+/* BaurLoss (losses/vqvae/vqvae.py:74-186, --loss=baur; its gdl_factor schedule: configure.py:56-76, handlers/general.py:92-118).  pred, target
+ * [BC, D, H, W] fp32 contiguous with D, H, W >= 3 (SA_EINVAL otherwise, and for null operands).  sums3 is OVERWRITTEN with (sum |p-y|, sum (p-y)^2,
+ * sum over the interior {1..D-2} x {1..H-2} x {1..W-2} of t_z + t_y + t_x), t_a(i) = | |y(i-e_a) - y(i)| - |p(i-e_a) - p(i)| |.  grad (if != NULL)
+ * = gscale * d (l1 + l2 + gdl_factor * gdl) / d pred with torch's sign(0) = 0 subgradients; l1, l2 are means over n = BC D H W and gdl over
+ * m = BC (D-2)(H-2)(W-2), or plain sums when reduction_sum != 0.  Fixed summation order: bitwise reproducible.  gdl_factor == 0 skips the stencil
+ * (sums3[2] = 0).  ws: sa_baur_loss_workspace_bytes(BC, D, H, W) bytes (SA_EINVAL for a bad shape). */
+int sa_baur_loss(const float *pred, const float *target, int64_t BC, int D, int H, int W, float gdl_factor, int reduction_sum, float gscale, float *sums3,
+                 float *grad, float *ws, void *stream);
+int64_t sa_baur_loss_workspace_bytes(int64_t BC, int D, int H, int W);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -5,7 +5,8 @@
         --experiment_name=exp --mode=training|extracting|decoding  [--no_levels=4 --no_channels=256 ...]
 
 MONAI/ignite/fire/deepspeed are not on the target, so the loop is a minimal in-house one: Adam + per-iteration ExponentialLR
-(run_vqvae.py:82-91,162), losses "mse" and "jukebox" (spectral; the LPIPS family is out of scope), optional adversarial component
+(run_vqvae.py:82-91,162), losses "mse", "jukebox" (spectral) and "baur" (L1 + L2 + image-gradient difference, its factor scheduled per epoch
+by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_factor_value; the LPIPS family is out of scope), optional adversarial component
 (src/engines/trainer.py semantics incl. the adaptive weight; criteria vanilla / hinge / least_square), checkpoints with the reference's keys
 (network, optimizer, lr_scheduler, trainer, d_*) restored on resume, uint16 ``.npy`` code files.
 Inputs: ``.npy`` volumes (any of dir / glob / csv listing) or ``synthetic:<n>`` (uniform [0,1) volumes of ``--roi`` size).
@@ -90,10 +91,11 @@ def _validation_mse(net, files, cfg, gen, dev, rank, world):
 def training(cfg, rank, local, world, dev):
     from synthanatomy_amd.engines.trainer import AdversarialTrainer
     from synthanatomy_amd.losses.adversarial import get_discriminator_loss, get_generator_loss
-    from synthanatomy_amd.losses.vqvae import get_vqvae_loss
+    from synthanatomy_amd.losses.vqvae import gdl_factor_schedule, get_vqvae_loss
     from synthanatomy_amd.runtime.ddp import GradReducer
     from synthanatomy_amd.runtime.optim import ExponentialLR, FlatParams, FusedAdam, TrainerState
     loss_fn = get_vqvae_loss(cfg)
+    baur = cfg["loss"] == "baur"      # gdl_factor scheduled at every finished epoch (src/losses/vqvae/configure.py:56-76)
     net = build_network(cfg, dev).train()
     flat = FlatParams(net.parameters())
     red = GradReducer(flat)
@@ -138,6 +140,8 @@ def training(cfg, rank, local, world, dev):
         state.rebase(epoch_length, cfg["epochs"])      # finished epochs by the CHECKPOINT's epoch length; this run's data set / --epochs decide the rest
         net.invalidate_packed_weights()
         log(rank, f"resumed from {ckpt}: epoch {state.epoch}, iteration {state.iteration}, lr {opt.lr:.6e}")
+        if baur and state.epoch > 0:      # (upstream restarts at the class default 0.0 for this epoch; resuming equals not stopping here)
+            loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, state.epoch))
     gen = torch.Generator(device=dev).manual_seed(cfg["seed"] + rank)
     for epoch in range(state.epoch, cfg["epochs"]):
         # DistributedSampler semantics: one epoch-seeded permutation shared by all ranks, padded so every rank runs the same number of steps
@@ -159,10 +163,14 @@ def training(cfg, rank, local, world, dev):
             done += 1
             if state.iteration % cfg["log_every"] == 0:
                 extra = f" g_loss {float(res['g_loss']):.6f} d_loss {float(res['d_loss']):.6f} adv_weight {float(res['adversarial_weight']):.4f}" if res else ""
+                if baur:
+                    extra += f" gdl_factor {loss_fn.get_gdl_factor():.6g}"
                 log(rank, f"epoch {epoch} it {state.iteration} loss {loss.item():.6f}{extra} perplexity {net.get_perplexity()[0].item():.2f} lr {opt.lr:.3e}")
             if done == epoch_length:
                 break
         state.iteration = (epoch + 1) * epoch_length      # (a short last batch list still closes the epoch)
+        if baur:                                          # ParamSchedulerHandler(epoch_level=True) at EPOCH_COMPLETED, state.epoch = finished epochs
+            loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, epoch + 1))
         if (epoch + 1) % cfg["eval_every"] == 0 and val_files:
             mse = _validation_mse(net, val_files, cfg, gen, dev, rank, world)
             log(rank, f"epoch {epoch} validation mse {mse:.6f}")

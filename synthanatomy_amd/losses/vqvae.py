@@ -106,11 +106,109 @@ class JukeboxLoss(torch.nn.Module):
         return self.get_fft_factor()
 
 
-VQVAE_LOSSES = ("mse", "jukebox")   # of the reference's src/losses/vqvae/utils.py list; the LPIPS / Hartley / WaveGAN families are out of scope
+class _BaurFn(torch.autograd.Function):
+    """``l1 + l2 + gdl_factor * gdl`` and its gradient in one ``sa_baur_loss`` launch pair (csrc/losses.hip).  Returns the differentiable sum and the
+    three terms as non-differentiable side outputs (the summaries)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, gdl_factor, reduction_sum):
+        _ffi.require_gpu()
+        a = pred.contiguous()
+        b = target.contiguous().to(a.device)
+        B, C, D, H, W = a.shape
+        lib = _ffi.lib()
+        ws_bytes = lib.sa_baur_loss_workspace_bytes(B * C, D, H, W)
+        _ffi.check(ws_bytes if ws_bytes < 0 else 0, "sa_baur_loss_workspace_bytes")
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=a.device)
+        sums = torch.empty(3, dtype=torch.float32, device=a.device)
+        grad = torch.empty_like(a) if pred.requires_grad else None
+        _ffi.check(lib.sa_baur_loss(_ffi.ptr(a), _ffi.ptr(b), B * C, D, H, W, float(gdl_factor), int(reduction_sum), 1.0, _ffi.ptr(sums), _ffi.ptr(grad),
+                                    _ffi.ptr(ws), _ffi.stream()), "sa_baur_loss")
+        if reduction_sum:
+            l1, l2, gdl = sums[0], sums[1], sums[2] * gdl_factor
+        else:
+            l1, l2, gdl = sums[0] / a.numel(), sums[1] / a.numel(), sums[2] / (B * C * (D - 2) * (H - 2) * (W - 2)) * gdl_factor
+        rec = l1 + l2 + gdl
+        ctx.grad = grad
+        ctx.mark_non_differentiable(l1, l2, gdl)
+        return rec, l1, l2, gdl
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        # re-entrant like _MSEFn: the stored d loss / d pred is neither consumed nor scaled in place
+        grad = ctx.grad
+        return (grad * g if grad is not None else None), None, None, None
+
+
+class BaurLoss(torch.nn.Module):
+    """``BaurLoss`` of the reference (src/losses/vqvae/vqvae.py:74-186, selected by ``--loss=baur``): ``l1(pred, y) + mse(pred, y) +
+    gdl * gdl_factor + sum(quantization_losses)``, where ``gdl`` reduces ``| |y(i - e_a) - y(i)| - |pred(i - e_a) - pred(i)| |`` summed over the
+    three axes on the interior voxels (the reference's ConstantPad3d shifts cropped by ``[1:-1]`` on D, H and W).  The three reductions and
+    d loss / d pred are one fused HIP pass (``sa_baur_loss``, csrc/losses.hip).  ``gdl_factor`` starts at 0.0; ``run_vqvae.py`` schedules it once per
+    epoch with :func:`gdl_factor_schedule`.  Same constructor, ``summaries`` keys and ``get/set_gdl_factor`` as upstream."""
+
+    def __init__(self, size_average: bool = None, reduce: bool = None, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("sum", "mean"):
+            raise ValueError("Reduction must be either 'sum' or 'mean'")
+        self.reduction = reduction
+        self.gdl_factor: float = 0.0
+        self.summaries: Dict = {"scalar": {}}
+
+    def forward(self, network_output: Dict[str, List[torch.Tensor]], y: torch.Tensor) -> torch.Tensor:
+        y = y.float()
+        y_pred = network_output["reconstruction"][0].float()
+        if y_pred.dim() != 5 or min(y_pred.shape[2:]) < 3:
+            raise ValueError(f"BaurLoss needs [B, C, D, H, W] volumes with D, H, W >= 3 (the image-gradient term crops one voxel per side); "
+                             f"got {tuple(y_pred.shape)}")
+        if tuple(y.shape) != tuple(y_pred.shape):
+            raise ValueError(f"BaurLoss: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
+        loss, l1, l2, gdl = _BaurFn.apply(y_pred, y, float(self.gdl_factor), self.reduction == "sum")
+        self.summaries["scalar"]["Loss-MAE-Reconstruction"] = l1.detach()
+        self.summaries["scalar"]["Loss-MSE-Reconstruction"] = l2.detach()
+        self.summaries["scalar"]["Loss-GDL-Reconstruction"] = gdl.detach()
+        self.summaries["scalar"]["Auxiliary-GDL_Factor"] = self.gdl_factor
+        for idx, ql in enumerate(network_output["quantization_losses"]):
+            ql = ql.float()
+            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
+            loss = loss + ql
+        return loss
+
+    def get_summaries(self):
+        return self.summaries
+
+    def get_gdl_factor(self) -> float:
+        return self.gdl_factor
+
+    def set_gdl_factor(self, gdl_factor: float) -> float:
+        self.gdl_factor = gdl_factor
+        return self.get_gdl_factor()
+
+
+def gdl_factor_schedule(config: dict, finished_epochs: int) -> float:
+    """The ``gdl_factor`` of ``--loss=baur`` after ``finished_epochs`` epochs: ``ParamSchedulerHandler._linear`` (reference src/handlers/general.py:92-118)
+    with the four ``--*_factor_*`` flags (src/losses/vqvae/configure.py:56-76), called at EPOCH_COMPLETED with ignite's ``state.epoch``.  Kept as
+    upstream writes it, quirks included: before ``initial_factor_steps`` it returns ``2 * initial_factor_value`` (``delta = initial_value`` is added to
+    ``initial_value``), and the ramp divides by ``max_factor_steps``, not by its length."""
+    init, const = config["initial_factor_value"], config["initial_factor_steps"]
+    steps, top = config["max_factor_steps"], config["max_factor_value"]
+    s = finished_epochs
+    if s < const:
+        delta = init
+    elif s > steps:
+        delta = top - init
+    else:
+        delta = (top - init) * ((s - const) / steps)
+    return init + delta
+
+
+VQVAE_LOSSES = ("baur", "mse", "jukebox")   # of the reference's src/losses/vqvae/utils.py list; the LPIPS / Hartley / WaveGAN families are out of scope
 
 
 def get_vqvae_loss(config: dict) -> torch.nn.Module:
     """src/losses/vqvae/configure.py:22-52 for the losses this build implements."""
+    if config["loss"] == "baur":
+        return BaurLoss()
     if config["loss"] == "mse":
         return MSELoss()
     if config["loss"] == "jukebox":
