@@ -211,6 +211,15 @@ int sa_mse(const float *a, const float *b, int64_t n, float *loss_sum, float *gr
 int sa_baur_loss(const float *pred, const float *target, int64_t BC, int D, int H, int W, float gdl_factor, int reduction_sum, float gscale, float *sums3,
                  float *grad, float *ws, void *stream);
 int64_t sa_baur_loss_workspace_bytes(int64_t BC, int D, int H, int W);
+/* MultiScaleSSIM metric (metrics/vqvae.py; pytorch_msssim 0.2.1 ms_ssim, run_vqvae.py:122-146 key metric).  x, y [B, C, D, H, W] fp32
+ * contiguous device tensors; win (win_size fp32 taps) and weights (levels fp32) are HOST arrays.  Every level runs on the stream, no host synchronisation.
+ * out_b[b] = mean over c of prod_l relu(cs_l)^w_l (l < levels-1) * relu(ssim_last)^w_last; level_means (may be NULL) gets [levels][B*C][2] = (mean ssim,
+ * mean cs) per level.  SA_EINVAL for null operands, an even win_size, min(H, W) <= (win_size-1)*16 (the package's assertion), and beyond the package:
+ * win_size outside 3..11, levels outside 1..8, a side < 2 or a level whose side is shorter than the window.  Fixed summation order, no atomics:
+ * bitwise reproducible, and a volume's value does not depend on the rest of the batch.  ws: sa_ms_ssim_workspace_bytes(...) bytes, 256-B aligned. */
+int sa_ms_ssim(const float *x, const float *y, int B, int C, int D, int H, int W, const float *win, int win_size, int levels, const float *weights,
+               float c1, float c2, float *out_b, float *level_means, void *ws, void *stream);
+int64_t sa_ms_ssim_workspace_bytes(int B, int C, int D, int H, int W, int win_size, int levels);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -68,11 +68,18 @@ def build_network(cfg, dev):
     return get_vqvae_network(cfg).to(dev)
 
 
-def _validation_mse(net, files, cfg, gen, dev, rank, world):
-    """Mean reconstruction MSE over the validation subjects (the evaluator of run_vqvae.py:248-289 with the metric this build has: the
-    reference's key metric is MS-SSIM, a MONAI metric outside the hot path; the selection rule -- keep the best one -- is the same)."""
+def _evaluate(net, files, cfg, gen, dev, rank, world, win_size):
+    """The evaluator of run_vqvae.py:122-146,248-289 over the validation subjects: ``mse`` is the mean reconstruction MSE this build has always
+    logged (``hip_mse``), ``metrics`` the reference's Metric-MS-SSIM_<w> (when ``win_size`` is not None), Metric-MAE and Metric-MSE-Reconstruction
+    (synthanatomy_amd.metrics.vqvae; each all-reduces its sum and count over the ranks in ``compute``)."""
     from synthanatomy_amd.losses.vqvae import hip_mse
+    from synthanatomy_amd.metrics.vqvae import MAE, MSE, MultiScaleSSIM
     import torch.distributed as dist
+    metrics = {}
+    if win_size is not None:
+        metrics[f"Metric-MS-SSIM_{win_size}-Reconstruction"] = MultiScaleSSIM(ms_ssim_kwargs={"win_size": win_size})
+    metrics["Metric-MAE-Reconstruction"] = MAE()
+    metrics["Metric-MSE-Reconstruction"] = MSE()
     was = net.training
     net.eval()
     tot = torch.zeros(2, device=dev, dtype=torch.float64)
@@ -82,10 +89,12 @@ def _validation_mse(net, files, cfg, gen, dev, rank, world):
             rec = net(x)["reconstruction"][0]
             tot[0] += hip_mse(rec, x).double() * x.shape[0]
             tot[1] += x.shape[0]
+            for m in metrics.values():
+                m.update((rec, x))
     if world > 1:
         dist.all_reduce(tot)
     net.train(was)
-    return float(tot[0] / tot[1].clamp(min=1))
+    return float(tot[0] / tot[1].clamp(min=1)), {k: m.compute() for k, m in metrics.items()}
 
 
 def training(cfg, rank, local, world, dev):
@@ -142,6 +151,14 @@ def training(cfg, rank, local, world, dev):
         log(rank, f"resumed from {ckpt}: epoch {state.epoch}, iteration {state.iteration}, lr {opt.lr:.6e}")
         if baur and state.epoch > 0:      # (upstream restarts at the class default 0.0 for this epoch; resuming equals not stopping here)
             loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, state.epoch))
+    # key metric (run_vqvae.py:122): MS-SSIM with get_ms_ssim_window's window; where the reference refuses to start (smallest side < 48), -MSE
+    from synthanatomy_amd.utils.vqvae import get_ms_ssim_window
+    try:
+        win_size = get_ms_ssim_window(cfg)
+    except ValueError as e:
+        win_size = None
+        log(rank, f"MS-SSIM key metric unavailable ({e}): the best checkpoint is chosen by -validation mse")
+    key_name = f"Metric-MS-SSIM_{win_size}-Reconstruction" if win_size is not None else None
     gen = torch.Generator(device=dev).manual_seed(cfg["seed"] + rank)
     for epoch in range(state.epoch, cfg["epochs"]):
         # DistributedSampler semantics: one epoch-seeded permutation shared by all ranks, padded so every rank runs the same number of steps
@@ -172,10 +189,14 @@ def training(cfg, rank, local, world, dev):
         if baur:                                          # ParamSchedulerHandler(epoch_level=True) at EPOCH_COMPLETED, state.epoch = finished epochs
             loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, epoch + 1))
         if (epoch + 1) % cfg["eval_every"] == 0 and val_files:
-            mse = _validation_mse(net, val_files, cfg, gen, dev, rank, world)
+            mse, metrics = _evaluate(net, val_files, cfg, gen, dev, rank, world, win_size)
             log(rank, f"epoch {epoch} validation mse {mse:.6f}")
-            if rank == 0:
-                save_checkpoint(cfg, epoch + 1, to_save, key_metric=-mse)      # evaluator's key-metric checkpoint, key_metric_n_saved=1
+            log(rank, f"epoch {epoch} validation " + " ".join(f"{k} {v:.6f}" for k, v in metrics.items()))
+            if rank == 0:                                                       # evaluator's key-metric checkpoint, key_metric_n_saved=1
+                if key_name is not None:
+                    save_checkpoint(cfg, epoch + 1, to_save, key_metric=metrics[key_name], key_metric_name=key_name)
+                else:
+                    save_checkpoint(cfg, epoch + 1, to_save, key_metric=-mse)
         if rank == 0 and (epoch + 1) % cfg["checkpoint_every"] == 0:
             save_checkpoint(cfg, epoch + 1, to_save)                            # ignite numbers checkpoints by finished epochs
     if rank == 0:

@@ -115,15 +115,17 @@ _BEST_SCORE = {}   # checkpoint directory -> (file, unrounded score) of the key-
 _SIDECAR = "checkpoint_key_metric.json"   # {"file": <basename>, "score": <unrounded float>} next to the key-metric checkpoint
 
 
-def _best_key_metric(ck, files):
+def _best_key_metric(ck, files, name=None):
     """Unrounded score of the existing key-metric checkpoint: from this process' memory, else from the small sidecar file this build writes next to
     it, else (files written by the reference, which stores no score; or a lost sidecar) parsed back from the file name.  The checkpoint itself is
-    never opened for this -- it holds the network, optimizer and discriminator states."""
+    never opened for this -- it holds the network, optimizer and discriminator states.  With ``name``, a best recorded under ANOTHER metric name
+    counts as absent (None): scores of different metrics are never compared.  A best without a recorded name (earlier sidecars, reference files)
+    is compared as before."""
     if not files:
         return None
     hit = _BEST_SCORE.get(os.path.abspath(ck))
     if hit is not None and hit[0] in files:
-        return hit[1]
+        return None if name is not None and hit[2] not in (None, name) else hit[1]
     side = None
     try:
         import json
@@ -135,6 +137,8 @@ def _best_key_metric(ck, files):
     for f in files:
         score = None
         if side and side.get("file") == os.path.basename(f):
+            if name is not None and side.get("name") not in (None, name):
+                continue
             score = side.get("score")
         if score is None:
             m = re.search(r"key_metric=(-?[0-9.]+(?:[eE][+-]?[0-9]+)?)\.pt$", f)
@@ -142,7 +146,7 @@ def _best_key_metric(ck, files):
                 continue
             score = float(m.group(1))
         if best is None or score > best[1]:
-            best = (f, float(score))
+            best = (f, float(score), side.get("name") if side and side.get("file") == os.path.basename(f) else None)
     if best is None:
         return None
     _BEST_SCORE[os.path.abspath(ck)] = best
@@ -155,7 +159,8 @@ def save_checkpoint(config, epoch, to_save: dict, key_metric: float = None, key_
     object's ``state_dict()``.  Periodic checkpoints are ``checkpoint_epoch=<e>.pt`` with ``n_saved=1``; with ``key_metric`` the file is the
     evaluator's ``checkpoint_key_metric=<value>.pt`` (``key_metric_n_saved=1``: kept only while it is the best so far); its unrounded score goes
     to the sidecar ``checkpoint_key_metric.json`` (ignite compares the score it keeps in memory; the file name only carries a rounded copy, and
-    validation MSEs below 1e-4 must still order correctly after a restart)."""
+    validation MSEs below 1e-4 must still order correctly after a restart).  ``key_metric_name`` is recorded in the sidecar as ``"name"``; a best
+    recorded under another name is replaced, never compared against."""
     if not isinstance(to_save, dict):   # round-1 call form: save_checkpoint(cfg, epoch, network, optimizer)
         raise TypeError("to_save must be a dict of name -> object with state_dict()")
     obj = {k: _state(v) for k, v in to_save.items() if v is not None}
@@ -168,15 +173,18 @@ def save_checkpoint(config, epoch, to_save: dict, key_metric: float = None, key_
                 os.remove(f)
         return path
     old = glob.glob(os.path.join(ck, "checkpoint_key_metric=*.pt"))
-    best = _best_key_metric(ck, old)
+    best = _best_key_metric(ck, old, key_metric_name)
     if best is not None and key_metric <= best:
         return None
     path = os.path.join(ck, f"checkpoint_key_metric={key_metric:.4f}.pt")
     torch.save(obj, path)
     import json
+    side = {"file": os.path.basename(path), "score": float(key_metric)}
+    if key_metric_name is not None:
+        side["name"] = key_metric_name
     with open(os.path.join(ck, _SIDECAR), "w") as f:
-        json.dump({"file": os.path.basename(path), "score": float(key_metric)}, f)
-    _BEST_SCORE[os.path.abspath(ck)] = (path, float(key_metric))
+        json.dump(side, f)
+    _BEST_SCORE[os.path.abspath(ck)] = (path, float(key_metric), key_metric_name)
     for f in old:
         if f != path:
             os.remove(f)
