@@ -211,6 +211,21 @@ int sa_mse(const float *a, const float *b, int64_t n, float *loss_sum, float *gr
 int sa_baur_loss(const float *pred, const float *target, int64_t BC, int D, int H, int W, float gdl_factor, int reduction_sum, float gscale, float *sums3,
                  float *grad, float *ws, void *stream);
 int64_t sa_baur_loss_workspace_bytes(int64_t BC, int D, int H, int W);
+/* SpectralLoss (losses/vqvae/vqvae.py:188-323, --loss=spectral), HartleyLoss (:326-519, --loss=hartley), WaveGANLoss (:641-771, --loss=wavegan):
+ * the spectral terms over half spectra.  xp, xy = the UNNORMALISED rfftn of pred and target over (C, D, H, W): [B, C, D, H, W/2 + 1] complex64
+ * (interleaved re, im), B, C >= 1 and D, H, W >= 2 (SA_EINVAL otherwise, for a bad kind and for null xp / xy / sums / ws; SA_EUNSUPPORTED beyond 2^31
+ * bins).  With Y = X / sqrt(C D H W) (the reference's ortho spectra), A = |Y|, m = the bin's multiplicity (1 on k_W = 0 and, W even, k_W = W/2;
+ * 2 elsewhere), sums[3] (fp64) is OVERWRITTEN with
+ *   SA_FOURIER_SPECTRAL: (sum m (Ap - Ay)^2, sum m (1 - exp|phi_p - phi_y|)^2, 0)     phi = atan2, Im forced to +0 on the self-conjugate bins
+ *   SA_FOURIER_HARTLEY:  (sum m w^2 |Yp - Yy|^2, 0, 0)    w = 1, or (prioritise_hf) the reference's high-frequency weight (vqvae.py:440-497)
+ *   SA_FOURIER_WAVEGAN:  (sum m (Ay - Ap)^2, sum m Ay^2, sum m |log Ay - log Ap|)
+ * grad (if != NULL; it may alias xp) = factor * the Hermitian half of d loss / d Yp divided by sqrt(C D H W), where loss is (sums[0] + sums[1]) / 2n,
+ * sums[0] / 2n and sqrt(sums[0] / sums[1]) + sums[2] / n respectively (n = B C D H W): irfftn(grad, norm="forward") over (C, D, H, W) is
+ * factor * d loss / d pred.  Fixed summation order: bitwise reproducible.  ws: sa_fourier_loss_workspace_bytes(B, C, D, H, W) bytes. */
+enum { SA_FOURIER_SPECTRAL = 0, SA_FOURIER_HARTLEY = 1, SA_FOURIER_WAVEGAN = 2 };
+int sa_fourier_loss(int kind, const float *xp, const float *xy, int64_t B, int C, int D, int H, int W, int prioritise_hf, float factor, double *sums,
+                    float *grad, void *ws, void *stream);
+int64_t sa_fourier_loss_workspace_bytes(int64_t B, int C, int D, int H, int W);
 /* MultiScaleSSIM metric (metrics/vqvae.py; pytorch_msssim 0.2.1 ms_ssim, run_vqvae.py:122-146 key metric).  x, y [B, C, D, H, W] fp32
  * contiguous device tensors; win (win_size fp32 taps) and weights (levels fp32) are HOST arrays.  Every level runs on the stream, no host synchronisation.
  * out_b[b] = mean over c of prod_l relu(cs_l)^w_l (l < levels-1) * relu(ssim_last)^w_last; level_means (may be NULL) gets [levels][B*C][2] = (mean ssim,

@@ -5,7 +5,8 @@
         --experiment_name=exp --mode=training|extracting|decoding  [--no_levels=4 --no_channels=256 ...]
 
 MONAI/ignite/fire/deepspeed are not on the target, so the loop is a minimal in-house one: Adam + per-iteration ExponentialLR
-(run_vqvae.py:82-91,162), losses "mse", "jukebox" (spectral) and "baur" (L1 + L2 + image-gradient difference, its factor scheduled per epoch
+(run_vqvae.py:82-91,162), losses "mse", "jukebox" (spectral), "spectral" / "hartley" / "wavegan" (FFT amplitude + phase, weighted Hartley and
+spectral convergence + log magnitude; their factors are not scheduled, as upstream) and "baur" (L1 + L2 + image-gradient difference, its factor scheduled per epoch
 by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_factor_value; the LPIPS family is out of scope), optional adversarial component
 (src/engines/trainer.py semantics incl. the adaptive weight; criteria vanilla / hinge / least_square), checkpoints with the reference's keys
 (network, optimizer, lr_scheduler, trainer, d_*) restored on resume, uint16 ``.npy`` code files.

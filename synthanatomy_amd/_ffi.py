@@ -99,6 +99,8 @@ _SIGS = {
     "sa_mse_det": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "sa_baur_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sa_baur_loss_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "sa_fourier_loss": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sa_fourier_loss_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
     "sa_ms_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p,
                            c_void_p, c_void_p]),
     "sa_ms_ssim_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -202,7 +202,180 @@ def gdl_factor_schedule(config: dict, finished_epochs: int) -> float:
     return init + delta
 
 
-VQVAE_LOSSES = ("baur", "mse", "jukebox")   # of the reference's src/losses/vqvae/utils.py list; the LPIPS / Hartley / WaveGAN families are out of scope
+_FOURIER_KIND = {"spectral": 0, "hartley": 1, "wavegan": 2}   # include/synthanatomy_hip.h: SA_FOURIER_*
+_FFT_DIMS = (1, 2, 3, 4)
+
+
+class _FourierFn(torch.autograd.Function):
+    """The spectral term of ``SpectralLoss`` / ``HartleyLoss`` / ``WaveGANLoss`` and its gradient: unnormalised rocFFT ``rfftn`` of both volumes over
+    (C, D, H, W), one fused ``sa_fourier_loss`` pass over the two half spectra (csrc/spectral.hip) that writes the fp64 sums and, in place of the
+    prediction's spectrum, the spectrum-domain gradient, then ``irfftn(norm="forward")`` of that gradient.  Returns the differentiable spectral term
+    (factor applied) and the two unscaled summary terms as non-differentiable side outputs."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind, factor, prioritise_hf):
+        _ffi.require_gpu()
+        a = pred.contiguous()
+        B, C, D, H, W = a.shape
+        lib = _ffi.lib()
+        ws_bytes = lib.sa_fourier_loss_workspace_bytes(B, C, D, H, W)
+        _ffi.check(ws_bytes if ws_bytes < 0 else 0, "sa_fourier_loss_workspace_bytes")
+        # (the kernel indexes bins as [B, C, D, H, W/2 + 1]; a multi-pass rocFFT transform leaves its output re-strided, k_W not innermost)
+        xp = torch.fft.rfftn(a, dim=_FFT_DIMS, norm="backward").contiguous()
+        xy = torch.fft.rfftn(target.contiguous().to(a.device), dim=_FFT_DIMS, norm="backward").contiguous()
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=a.device)
+        sums = torch.empty(3, dtype=torch.float64, device=a.device)
+        want = pred.requires_grad
+        _ffi.check(lib.sa_fourier_loss(_FOURIER_KIND[kind], _ffi.ptr(xp), _ffi.ptr(xy), B, C, D, H, W, int(prioritise_hf), float(factor), _ffi.ptr(sums),
+                                       _ffi.ptr(xp) if want else None, _ffi.ptr(ws), _ffi.stream()), "sa_fourier_loss")
+        ctx.grad = torch.fft.irfftn(xp, s=(C, D, H, W), dim=_FFT_DIMS, norm="forward") if want else None
+        n = a.numel()
+        if kind == "spectral":
+            t1, t2 = sums[0] * (0.5 / n), sums[1] * (0.5 / n)          # amplitude, phase
+            spec = (t1 + t2) * factor
+        elif kind == "hartley":
+            spec = sums[0] * (0.5 / n) * factor
+            t1, t2 = spec.clone(), torch.zeros_like(spec)               # (the reference's Hartley summary is the scaled term; distinct tensors, since
+                                                                        # the side outputs are marked non-differentiable)
+        else:
+            t1, t2 = torch.sqrt(sums[0]) / torch.sqrt(sums[1]), sums[2] / n     # spectral convergence, log magnitude
+            spec = (t1 + t2) * factor
+        dt = torch.float64 if kind == "hartley" and prioritise_hf else torch.float32   # (the reference's Hartley weight is float64)
+        spec, t1, t2 = spec.to(dt), t1.to(dt), t2.to(dt)
+        ctx.mark_non_differentiable(t1, t2)
+        return spec, t1, t2
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        # re-entrant like _MSEFn: the stored d loss / d pred is neither consumed nor scaled in place
+        grad = ctx.grad
+        return (grad * g.float() if grad is not None else None), None, None, None, None
+
+
+class _FourierLoss(torch.nn.Module):
+    _KIND = ""
+    _FACTOR_ATTR, _FACTOR_KEY = "fft_factor", "Auxiliary-FFT_Factor"      # the factor's attribute and summary key, as upstream names them
+
+    def __init__(self, dimensions: int, include_pixel_loss: bool = True, fft_kwargs: Dict = None, size_average: bool = None, reduce: bool = None,
+                 reduction: str = "mean"):
+        super().__init__()
+        name = type(self).__name__
+        if dimensions != 3:
+            raise NotImplementedError(f"{name}: only dimensions=3 ([B, C, D, H, W] volumes) has a HIP path; got dimensions={dimensions}")
+        default = {"s": None, "dim": tuple(range(1, dimensions + 2)), "norm": "ortho"}
+        if fft_kwargs is not None and dict(fft_kwargs) != default:
+            raise NotImplementedError(f"{name}: only the default fft_kwargs {default} have a HIP path; got {fft_kwargs}")
+        if reduction not in ("mean", "sum"):
+            raise NotImplementedError(f"{name}: reduction must be 'mean' or 'sum' (it applies to the pixel term); got {reduction!r}")
+        self.dimensions, self.include_pixel_loss, self.reduction = dimensions, include_pixel_loss, reduction
+        self.fft_kwargs = default
+        self.summaries: Dict = {"scalar": {}}
+        setattr(self, self._FACTOR_ATTR, 1.0)
+
+    def _spectral_summaries(self, spec, t1, t2):
+        raise NotImplementedError
+
+    def _prioritise_hf(self) -> bool:
+        return False
+
+    def forward(self, network_output: Dict[str, List[torch.Tensor]], y: torch.Tensor) -> torch.Tensor:
+        y = y.float()
+        y_pred = network_output["reconstruction"][0].float()
+        name = type(self).__name__
+        if y_pred.dim() != 5 or min(y_pred.shape[2:]) < 2:
+            raise ValueError(f"{name} needs [B, C, D, H, W] volumes with D, H, W >= 2; got {tuple(y_pred.shape)}")
+        if tuple(y.shape) != tuple(y_pred.shape):
+            raise ValueError(f"{name}: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
+        factor = getattr(self, self._FACTOR_ATTR)
+        loss, t1, t2 = _FourierFn.apply(y_pred, y, self._KIND, float(factor), self._prioritise_hf())
+        self._spectral_summaries(loss.detach(), t1.detach(), t2.detach())
+        self.summaries["scalar"][self._FACTOR_KEY] = factor
+        if self.include_pixel_loss:
+            l2 = hip_mse(y_pred, y)
+            if self.reduction == "sum":
+                l2 = l2 * y_pred.numel()
+            self.summaries["scalar"]["Loss-MSE-Reconstruction"] = l2.detach()
+            loss = loss + l2
+        for idx, ql in enumerate(network_output["quantization_losses"]):
+            ql = ql.float()
+            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
+            loss = loss + ql
+        return loss
+
+    def get_summaries(self):
+        return self.summaries
+
+
+class SpectralLoss(_FourierLoss):
+    """``SpectralLoss(dimensions=3)`` of the reference (src/losses/vqvae/vqvae.py:188-323, ``--loss=spectral``): ``fft_factor * (0.5 mse(|Y_pred|, |Y|)
+    + mean 0.5 (1 - exp|angle Y_pred - angle Y|)^2) + mse(pred, y) + sum(quantization_losses)``, Y the ortho ``fftn`` over dims (1, 2, 3, 4).  The
+    spectral term and its gradient are :class:`_FourierFn` (half spectra, one fused HIP pass).  Same constructor, ``summaries`` keys and
+    ``get/set_fft_factor`` as upstream; a non-default ``fft_kwargs`` or ``dimensions`` raises ``NotImplementedError``."""
+    _KIND = "spectral"
+
+    def _spectral_summaries(self, spec, amp, phase):
+        self.summaries["scalar"]["Loss-Amplitude-Reconstruction"] = amp
+        self.summaries["scalar"]["Loss-Phase-Reconstruction"] = phase
+        self.summaries["scalar"]["Loss-Spectral-Reconstruction"] = spec
+
+    def get_fft_factor(self) -> float:
+        return self.fft_factor
+
+    def set_fft_factor(self, fft_factor: float) -> float:
+        self.fft_factor = fft_factor
+        return self.get_fft_factor()
+
+
+class HartleyLoss(_FourierLoss):
+    """``HartleyLoss(dimensions=3)`` of the reference (src/losses/vqvae/vqvae.py:326-519, ``--loss=hartley``): ``fht_factor * 0.5 mse(w H_pred, w H)
+    + mse(pred, y) + sum(quantization_losses)``, H = Re - Im of the ortho ``fftn`` and w the reference's high-frequency weight (1 with
+    ``prioritise_high_frequency=False``).  Because w is symmetric under k -> -k this is a weighted complex MSE, computed on half spectra by
+    :class:`_FourierFn`.  As upstream, the loss is float64 when the weight applies (the reference builds it in float64).  Same constructor,
+    ``summaries`` keys and ``get/set_fht_factor`` as upstream."""
+    _KIND = "hartley"
+    _FACTOR_ATTR, _FACTOR_KEY = "fht_factor", "Auxiliary-Hartley_Factor"
+
+    def __init__(self, dimensions: int, include_pixel_loss: bool = True, fft_kwargs: Dict = None, prioritise_high_frequency: bool = True,
+                 size_average: bool = None, reduce: bool = None, reduction: str = "mean"):
+        super().__init__(dimensions, include_pixel_loss, fft_kwargs, size_average, reduce, reduction)
+        self.prioritise_high_frequency = prioritise_high_frequency
+
+    def _prioritise_hf(self) -> bool:
+        return bool(self.prioritise_high_frequency)
+
+    def _spectral_summaries(self, spec, *_):
+        self.summaries["scalar"]["Loss-Hartley-Reconstruction"] = spec
+
+    def get_fht_factor(self) -> float:
+        return self.fht_factor
+
+    def set_fht_factor(self, fht_factor: float) -> float:
+        self.fht_factor = fht_factor
+        return self.get_fht_factor()
+
+
+class WaveGANLoss(_FourierLoss):
+    """``WaveGANLoss(dimensions=3)`` of the reference (src/losses/vqvae/vqvae.py:641-771, ``--loss=wavegan``): ``fft_factor * (||A - A_pred||_F / ||A||_F
+    + l1(log A, log A_pred)) + mse(pred, y) + sum(quantization_losses)``, A = |ortho fftn|.  The two norms are global, so the fused HIP step takes a
+    second pass for the gradient, reading the finished sums on the device.  Same constructor, ``summaries`` keys and ``get/set_fft_factor`` as
+    upstream."""
+    _KIND = "wavegan"
+
+    def _spectral_summaries(self, spec, l_sc, l_mag):
+        self.summaries["scalar"]["Loss-Spectral_Convergence-Reconstruction"] = l_sc
+        self.summaries["scalar"]["Loss-Log_Magnitude-Reconstruction"] = l_mag
+        self.summaries["scalar"]["Loss-Spectral-Reconstruction"] = spec
+
+    def get_fft_factor(self) -> float:
+        return self.fft_factor
+
+    def set_fft_factor(self, fft_factor: float) -> float:
+        self.fft_factor = fft_factor
+        return self.get_fft_factor()
+
+
+# of the reference's src/losses/vqvae/utils.py list; the LPIPS family (perceptual, jukebox_perceptual, hartley_perceptual, baseline) is out of scope
+VQVAE_LOSSES = ("baur", "mse", "jukebox", "spectral", "hartley", "wavegan")
 
 
 def get_vqvae_loss(config: dict) -> torch.nn.Module:
@@ -213,4 +386,10 @@ def get_vqvae_loss(config: dict) -> torch.nn.Module:
         return MSELoss()
     if config["loss"] == "jukebox":
         return JukeboxLoss(dimensions=3)
+    if config["loss"] == "spectral":
+        return SpectralLoss(dimensions=3)
+    if config["loss"] == "hartley":
+        return HartleyLoss(dimensions=3)
+    if config["loss"] == "wavegan":
+        return WaveGANLoss(dimensions=3)
     raise ValueError(f"Loss function unknown. Was given {config['loss']} but choices are {list(VQVAE_LOSSES)}.")
