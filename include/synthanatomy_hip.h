@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4   /* 4 (round 6): + sa_rotary_pairs, sa_subpixel_pool_fwd / _bwd, sa_comm_* (additions only; developer switches SA_DBG_CELLS / SA_DBG_DENSE_RING retired).  3 (round 5): sa_sample_step takes top_k.  2 (round 4): sa_local_attn_fwd/bwd + sa_epilogue grew trailing pointers in round 3, SA_F16 operand type, sa_mse partials; a caller built against 1 must not load this library */
+#define SA_ABI_VERSION 5   /* 5: the second tier of the FAVOR+ scans left (the one-block / segmented scan entry points, the separate prefix-sum and normaliser passes) with two developer switches (bits 1 and 8 unassigned); a caller built against 4 that binds them must not load this library.  4 (round 6): + sa_rotary_pairs, sa_subpixel_pool_fwd / _bwd, sa_comm_* (additions only; developer switches SA_DBG_CELLS / SA_DBG_DENSE_RING retired).  3 (round 5): sa_sample_step takes top_k.  2 (round 4): sa_local_attn_fwd/bwd + sa_epilogue grew trailing pointers in round 3, SA_F16 operand type, sa_mse partials; a caller built against 1 must not load this library */
 enum { SA_F32 = 0, SA_BF16 = 1, SA_F16 = 2 /* IEEE half: FORWARD operand / activation type only (the reference's AMP dtype, src/engines/trainer.py:161-163); see sa_conv_fprop */ };
 enum { SA_ACT_NONE = 0, SA_ACT_RELU = 1, SA_ACT_LRELU = 2, SA_ACT_GELU = 3 };
 enum { SA_MASK_NONE = 0, SA_MASK_POS = 1 /* out *= (mask > 0) */, SA_MASK_LRELU = 2 /* out *= mask>0 ? 1 : slope */,
@@ -84,14 +84,12 @@ int sa_kernel_log_read(char *buf, int cap, int stop);
  * (SA_NO_HALO=1 ...), never re-read by a launch.  sa_set_debug_flags returns the previous value.  Launches read it without locking: set
  * it while no other thread is inside the library. */
 #define SA_DBG_NO_HALO           (1u << 0)   /* 3x3x3 convs on the im2col-order kernels instead of the halo mainloops (fprop, dgrad, wgrad) */
-#define SA_DBG_NO_HALO256        (1u << 1)   /* 128-voxel halo tiles only */
 #define SA_DBG_NO_HALO256_FUSE   (1u << 2)   /* fused residual block on the 128-voxel halo kernel */
 #define SA_DBG_NO_DMA            (1u << 3)   /* register-staged mainloops instead of buffer_load ... lds */
 #define SA_DBG_NO_SMALL_TILES    (1u << 4)   /* keep 128x128 tiles for small dense grids */
 #define SA_DBG_NO_FUSED_DB       (1u << 5)   /* bias gradient by sa_colsum semantics inside wgrad disabled (separate pass) */
 #define SA_DBG_NO_WGRAD_HALO9    (1u << 6)   /* three-tap weight-gradient halo kernel instead of the nine-tap one */
 #define SA_DBG_IM2COL_DIRECT     (1u << 7)   /* sa_convt1_im2col without the LDS gather */
-#define SA_DBG_SCAN_VALU         (1u << 8)   /* FAVOR+ scans on the VALU segment kernels */
 #define SA_DBG_LOCAL_ATTN_EXACT  (1u << 9)   /* local attention on the exact-fp32 MFMA kernels */
 #define SA_DBG_HALO256_4W        (1u << 13)  /* bf16 im2col-order forward / data-gradient and weight-gradient kernels with four waves per block instead of eight */
 #define SA_DBG_RESERVED_14       (1u << 14)  /* (was SA_DBG_TILE256: 256 x 128 tiles for the im2col-order kernel -- measured slower, instance removed) */
@@ -330,22 +328,15 @@ int sa_favor_features_bwd(const float *dfeat, const float *feat, const float *dd
  * [nmat,nblk,d,d] scaled by |rows[nmat,m,d]| */
 int sa_favor_projection(const float *blocks, const float *rows, float *out, int nmat, int nblk, int m, int d, void *stream);
 /* causal running-state scans replacing fast_transformers' CausalDotProduct (forward and both backward directions):
- *   scan_a: T[m][d] += a_i[m] b_i[d] ; y_i[d] = (sum_m c_i[m] T[m][d]) * y_scale_i        (a, c: [B,N,G,LDF]; b, y: strided head blocks)
- *   scan_b: T[m][d] += a_i[m] b_i[d] ; y_i[m] = sum_d T[m][d] c_i[d] + ex_scale_i (ex_vec_i[m] + ex_const)   (y: [B,N,G,LDF])
- * state_ws (sa_favor_scan_workspace_bytes; NULL = one block per (b, g) walks all N positions) lets <= 16 segments of ~128
- * positions be scanned by independent blocks: segment state sums -> exclusive prefix -> segment scans from the prefix. */
-int64_t sa_favor_scan_workspace_bytes(int B, int N, int G, int LDF, int dv);
-int sa_favor_scan_a(const float *a, const float *c, const float *b, int b_stride, int b_off, const float *b_scale, float *y, int y_stride,
-                    int y_off, const float *y_scale, int B, int N, int G, int LDF, int dv, int reverse, int accumulate, float *state_ws,
-                    void *stream);
-int sa_favor_scan_b(const float *a, const float *b, int b_stride, int b_off, const float *b_scale, const float *c, int c_stride, int c_off,
-                    const float *c_scale, float *y, const float *ex_scale, const float *ex_vec, float ex_const, int B, int N, int G,
-                    int LDF, int dv, int reverse, float *state_ws, void *stream);
-/* The same scans with the column running sums fused (one extra state column on the chunked MFMA path; SA_EUNSUPPORTED elsewhere):
- * sa_favor_scan_a_norm: y_i = (sum_{j<=i} (c_i . a_j) b_j) / (c_i . (sum_{j<=i} a_j + den_eps)), inv_out[i] = 1 / denominator
- *                       (= sa_cumsum_rows + sa_favor_den + sa_favor_scan_a with y_scale = inv).
+ *   scan A: T[m][d] += a_i[m] b_i[d] b_scale_i ; y_i[d] = (sum_m c_i[m] T[m][d]) * y_scale_i   (a, c: [B,N,G,LDF]; b, y: strided head blocks)
+ *   scan B: T[m][d] += a_i[m] b_i[d] b_scale_i ; y_i[m] = sum_d T[m][d] c_i[d] c_scale_i + extra term   (y: [B,N,G,LDF])
+ * in chunks of 64 positions, every chunk an independent block: chunk state sums -> exclusive prefix over the chunks -> chunk outputs from the
+ * prefix, with the column running sums z = sum_j a_j riding along as one extra state column.  state_ws (sa_favor_scan_workspace_bytes) is
+ * required; LDF % 16 == 0, LDF <= 272 and dv == 64, anything else is SA_EUNSUPPORTED (there is no second, slower path).
+ * sa_favor_scan_a_norm: y_i = (sum_{j<=i} (c_i . a_j) b_j) / (c_i . (sum_{j<=i} a_j + den_eps)), inv_out[i] = 1 / denominator.
  * sa_favor_scan_b_cum : ex_mode 1: y_i[m] += ex_scale_i * (sum_{j<=i} a_j[m] + ex_const);  ex_mode 2: y_i[m] += sum_{j<=i} a_j[m] ex_scale_j
- *                       (j <= i in scan order; = sa_cumsum_rows + sa_favor_scan_b with ex_vec). */
+ *                       (j <= i in scan order). */
+int64_t sa_favor_scan_workspace_bytes(int B, int N, int G, int LDF, int dv);
 int sa_favor_scan_a_norm(const float *a, const float *c, const float *b, int b_stride, int b_off, float *y, int y_stride, int y_off, float *inv_out,
                          float den_eps, int B, int N, int G, int LDF, int dv, float *state_ws, int state_flags, void *stream);
 int sa_favor_scan_b_cum(const float *a, const float *b, int b_stride, int b_off, const float *b_scale, const float *c, int c_stride, int c_off,
@@ -379,8 +370,6 @@ int sa_favor_project_bwd(const float *ddd, const float *proj, const float *adden
  * tsum_ws (keys): at least one float of scratch (tsum_ws[0] = sum over the rows of the stabiliser's share, for the fix-up launch). */
 int sa_favor_features_project_bwd(const float *dfeat, const float *feat, const float *dd, const float *src, int src_stride, int heads, const float *proj,
                                   int is_query, float *dsrc, const void *gmax_ws, float *tsum_ws, int64_t rows, int m, int LDF, int dh, void *stream);
-int sa_cumsum_rows(const float *x, const float *scale, float *out, int B, int N, int G, int LDF, int reverse, float *seg_ws, void *stream);
-int sa_favor_den(const float *q, const float *z, float eps, float *inv, int64_t rows, int m, int LDF, void *stream);
 int sa_favor_dden(const float *dout, const float *out, int stride, int off, int G, int dv, const float *inv, float *dden, int64_t rows,
                   void *stream);
 /* rotary embedding of the local heads (local-attention >= 1.2); transpose=1 applies the adjoint (backward) */

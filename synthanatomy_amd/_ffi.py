@@ -134,18 +134,12 @@ _SIGS = {
                                       c_int64, c_int, c_int, c_void_p]),
     "sa_favor_projection": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sa_favor_scan_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "sa_favor_scan_a": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                c_int, c_int, c_void_p, c_void_p]),
-    "sa_favor_scan_b": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
-                                c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sa_favor_scan_a_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                      c_int, c_void_p]),
     "sa_favor_scan_b_cum": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
                                     c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "sa_favor_scan_a_state": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_int, c_void_p]),
-    "sa_cumsum_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "sa_favor_den": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "sa_favor_dden": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "sa_rotary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p]),
     "sa_comm_unique_id": (c_int, [c_void_p]),
@@ -229,7 +223,7 @@ def lib():
     return _lib
 
 
-ABI_VERSION = 4   # include/synthanatomy_hip.h: SA_ABI_VERSION
+ABI_VERSION = 5   # include/synthanatomy_hip.h: SA_ABI_VERSION
 SA_EINVAL, SA_EUNSUPPORTED, SA_ENOGPU = -1, -2, -3   # include/synthanatomy_hip.h
 
 

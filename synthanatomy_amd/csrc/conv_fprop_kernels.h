@@ -1204,7 +1204,7 @@ static int launch_fprop_halo(FpropArgs a, hipStream_t st) {
 // the 256-voxel variant: register epilogue only (full, aligned 128-channel tiles), 16 x 16 patches that tile the plane well
 static bool halo256_eligible(const FpropArgs& a, int sz) {
     const sa_conv_geom& g = a.g;
-    if (dbg(SA_DBG_NO_HALO256) || !halo_eligible(a, sz)) return false;
+    if (!halo_eligible(a, sz)) return false;
     if (g.cout_valid % 128 != 0 || (g.Cout & 7) != 0) return false;
     const int hp = (g.Ho + 15) / 16, wp = (g.Wo + 15) / 16;
     const double eff = (double)g.Ho * g.Wo / ((double)hp * 16 * wp * 16);

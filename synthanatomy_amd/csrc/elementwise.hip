@@ -28,7 +28,6 @@ static uint32_t flags_from_env() {
     auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     uint32_t f = 0;
     if (on("SA_NO_HALO")) f |= SA_DBG_NO_HALO;
-    if (on("SA_NO_HALO256")) f |= SA_DBG_NO_HALO256;
     if (on("SA_NO_HALO256_FUSE")) f |= SA_DBG_NO_HALO256_FUSE;
     if (on("SA_NO_DMA")) f |= SA_DBG_NO_DMA;
     if (on("SA_NO_SMALL_TILES")) f |= SA_DBG_NO_SMALL_TILES;
@@ -42,7 +41,6 @@ static uint32_t flags_from_env() {
     if (on("SA_FAVOR_SEQ_ALWAYS")) f |= SA_DBG_FAVOR_SEQ_ALWAYS;
     if (on("SA_NO_CELLS256")) f |= SA_DBG_NO_CELLS256;
     if (on("SA_NO_CLASS_LAUNCH")) f |= SA_DBG_NO_CLASS_LAUNCH;
-    if (on("SA_SCAN_VALU")) f |= SA_DBG_SCAN_VALU;
     if (num("SA_LOCAL_ATTN_EXACT", 0) == 1) f |= SA_DBG_LOCAL_ATTN_EXACT;
     f |= ((uint32_t)num("SA_SCAN_EXACT", 0) & 7u) << SA_DBG_SCAN_EXACT_SHIFT;
     return f;

@@ -484,131 +484,6 @@ struct ScanArgs {
     int32_t exact;         // host side: exact-fp32 MFMA kernels instead of the split-bf16 ones (state_flags bit 2)
 };
 
-constexpr int SCAN_TB = 8;  // positions staged per barrier
-
-// scan A: block = (b, g, 16-column slice); thread = (column dl = t&15, feature group mg = t>>4), features mg + 16 r
-__global__ __launch_bounds__(256) void favor_scan_a_kernel(const ScanArgs s) {
-    constexpr int NR = 17;  // LDF <= 272
-    __shared__ float sa_[SCAN_TB][272], sc_[SCAN_TB][272], sb_[SCAN_TB][16], sp_[SCAN_TB][16][17];
-    const int nsl = s.dv / 16;
-    const int seg = blockIdx.x % s.S, bx = blockIdx.x / s.S;
-    const int sl = bx % nsl, g = (bx / nsl) % s.G, b = bx / (nsl * s.G);
-    const int t = threadIdx.x, dl = t & 15, mg = t >> 4;
-    float* st = s.state ? s.state + (((int64_t)b * s.G + g) * s.S + seg) * s.LDF * s.dv : nullptr;
-    float T[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) T[r] = (s.pass == 2 && mg + 16 * r < s.LDF) ? st[(mg + 16 * r) * s.dv + sl * 16 + dl] : 0.f;
-    const int p0 = seg * s.seg_len, p1 = min(s.N, p0 + s.seg_len);
-    for (int i0 = p0; i0 < p1; i0 += SCAN_TB) {
-        const int nb = min(SCAN_TB, p1 - i0);
-        for (int e = t; e < nb * s.LDF; e += 256) {
-            const int k = e / s.LDF, c = e - k * s.LDF;
-            const int i = s.reverse ? s.N - 1 - (i0 + k) : i0 + k;
-            const int64_t row = ((int64_t)b * s.N + i) * s.G + g;
-            sa_[k][c] = s.a[row * s.LDF + c];
-            if (s.pass != 1) sc_[k][c] = s.c_feat[row * s.LDF + c];
-        }
-        if (t < nb * 16) {
-            const int k = t >> 4, d = t & 15;
-            const int i = s.reverse ? s.N - 1 - (i0 + k) : i0 + k;
-            const int64_t r = (int64_t)b * s.N + i;
-            float v = s.b[r * s.b_stride + s.b_off + g * s.dv + sl * 16 + d];
-            if (s.b_scale) v *= s.b_scale[r * s.G + g];
-            sb_[k][d] = v;
-        }
-        __syncthreads();
-        for (int k = 0; k < nb; ++k) {
-            const float bv = sb_[k][dl];
-            float p = 0.f;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const int mrow = mg + 16 * r;
-                if (mrow < s.LDF) {
-                    T[r] = fmaf(sa_[k][mrow], bv, T[r]);
-                    p = fmaf(sc_[k][mrow], T[r], p);
-                }
-            }
-            sp_[k][mg][dl] = p;
-        }
-        __syncthreads();
-        if (s.pass != 1 && t < nb * 16) {
-            const int k = t >> 4, d = t & 15;
-            float y = 0.f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) y += sp_[k][q][d];
-            const int i = s.reverse ? s.N - 1 - (i0 + k) : i0 + k;
-            const int64_t r = (int64_t)b * s.N + i;
-            if (s.y_scale) y *= s.y_scale[r * s.G + g];
-            float* yp = s.y + r * s.y_stride + s.y_off + g * s.dv + sl * 16 + d;
-            if (s.accumulate) *yp += y;
-            else *yp = y;
-        }
-        __syncthreads();
-    }
-    if (s.pass == 1) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-            if (mg + 16 * r < s.LDF) st[(mg + 16 * r) * s.dv + sl * 16 + dl] = T[r];
-    }
-}
-
-// scan B: block = (b, g, 64-feature slice); thread = (feature ml = t>>2, column quarter dq = t&3)
-__global__ __launch_bounds__(256) void favor_scan_b_kernel(const ScanArgs s) {
-    __shared__ float sa_[SCAN_TB][64], sb_[SCAN_TB][64], sc_[SCAN_TB][64];
-    const int nsl = (s.LDF + 63) / 64;
-    const int seg = blockIdx.x % s.S, bx = blockIdx.x / s.S;
-    const int sl = bx % nsl, g = (bx / nsl) % s.G, b = bx / (nsl * s.G);
-    const int t = threadIdx.x, ml = t >> 2, dq = t & 3;
-    const int mrow = sl * 64 + ml;
-    float* st = s.state ? s.state + (((int64_t)b * s.G + g) * s.S + seg) * s.LDF * s.dv : nullptr;
-    float T[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) T[j] = (s.pass == 2 && mrow < s.LDF) ? st[mrow * s.dv + dq * 16 + j] : 0.f;
-    const int p0 = seg * s.seg_len, p1 = min(s.N, p0 + s.seg_len);
-    for (int i0 = p0; i0 < p1; i0 += SCAN_TB) {
-        const int nb = min(SCAN_TB, p1 - i0);
-        for (int e = t; e < nb * 64; e += 256) {
-            const int k = e >> 6, c = e & 63;
-            const int i = s.reverse ? s.N - 1 - (i0 + k) : i0 + k;
-            const int64_t r = (int64_t)b * s.N + i;
-            const int64_t row = r * s.G + g;
-            sa_[k][c] = (sl * 64 + c < s.LDF) ? s.a[row * s.LDF + sl * 64 + c] : 0.f;
-            float bv = s.b[r * s.b_stride + s.b_off + g * s.dv + c];
-            if (s.b_scale) bv *= s.b_scale[row];
-            sb_[k][c] = bv;
-            float cv = 0.f;
-            if (s.pass != 1) {
-                cv = s.c_col[r * s.c_stride + s.c_off + g * s.dv + c];
-                if (s.c_scale) cv *= s.c_scale[row];
-            }
-            sc_[k][c] = cv;
-        }
-        __syncthreads();
-        for (int k = 0; k < nb; ++k) {
-            const float av = sa_[k][ml];
-            float p = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                T[j] = fmaf(av, sb_[k][dq * 16 + j], T[j]);
-                p = fmaf(T[j], sc_[k][dq * 16 + j], p);
-            }
-            p += __shfl_xor(p, 1, 64);
-            p += __shfl_xor(p, 2, 64);
-            if (s.pass != 1 && dq == 0 && mrow < s.LDF) {
-                const int i = s.reverse ? s.N - 1 - (i0 + k) : i0 + k;
-                const int64_t row = ((int64_t)b * s.N + i) * s.G + g;
-                if (s.ex_vec) p += (s.ex_scale ? s.ex_scale[row] : 1.f) * (s.ex_vec[row * s.LDF + mrow] + s.ex_const);
-                s.y[row * s.LDF + mrow] = p;
-            }
-        }
-        __syncthreads();
-    }
-    if (s.pass == 1 && mrow < s.LDF) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) st[mrow * s.dv + dq * 16 + j] = T[j];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ FAVOR+ scans on the fp32 MFMA
 // Chunked form of the same scans (64 positions per chunk, every chunk an independent block):
 //   1) chunk state sums      U_c = A_c^T B_c                    (favor_chunk_state_kernel)
@@ -1268,44 +1143,6 @@ __global__ void scan_state_prefix_kernel(float* __restrict__ state, int64_t BG, 
         p[k * elems] = acc;
         acc += v;
     }
-}
-
-// running (or reverse-running) sum along N of x[b,n,g,:] * scale[b,n,g]
-// pass 1 (segsum != NULL, out == NULL): per-segment totals.  pass 2: each segment starts from the sum of the totals before it.
-__global__ void cumsum_rows_kernel(const float* __restrict__ x, const float* __restrict__ scale, float* __restrict__ out, float* __restrict__ segsum,
-                                   int B, int N, int G, int LDF, int reverse, int S, int seg_len) {
-    const int64_t tix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tix >= (int64_t)B * G * LDF * S) return;
-    const int c = (int)(tix % LDF);
-    const int seg = (int)((tix / LDF) % S);
-    const int g = (int)((tix / ((int64_t)LDF * S)) % G);
-    const int b = (int)(tix / ((int64_t)LDF * S * G));
-    float* ss = segsum ? segsum + (((int64_t)b * G + g) * S) * LDF + c : nullptr;
-    float acc = 0.f;
-    if (out && ss)
-        for (int k = 0; k < seg; ++k) acc += ss[(int64_t)k * LDF];
-    const int p0 = seg * seg_len, p1 = min(N, p0 + seg_len);
-    for (int k = p0; k < p1; ++k) {
-        const int i = reverse ? N - 1 - k : k;
-        const int64_t row = ((int64_t)b * N + i) * G + g;
-        float v = x[row * LDF + c];
-        if (scale) v *= scale[row];
-        acc += v;
-        if (out) out[row * LDF + c] = acc;
-    }
-    if (!out) ss[(int64_t)seg * LDF] = acc;
-}
-
-// den[row] = sum_{c<m} q[row][c] * (z[row][c] + eps) ; inv[row] = 1/den    (one wave per row)
-__global__ void favor_den_kernel(const float* __restrict__ q, const float* __restrict__ z, float eps, float* __restrict__ inv, int64_t rows, int m,
-                                 int LDF) {
-    const int lane = threadIdx.x & 63;
-    const int64_t rp = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (rp >= rows) return;
-    float s = 0.f;
-    for (int c = lane; c < m; c += 64) s += q[rp * LDF + c] * (z[rp * LDF + c] + eps);
-    s = wave_sum(s);
-    if (lane == 0) inv[rp] = 1.f / s;
 }
 
 // dden[row] = -(dout . out) * invden  over the head's dv columns (one wave per (row, head))
@@ -2299,113 +2136,40 @@ extern "C" int sa_favor_projection(const float* blocks, const float* rows, float
     return 0;
 }
 
-static int check_scan(int B, int N, int G, int LDF, int dv) { return (B > 0 && N > 0 && G > 0 && LDF > 0 && LDF <= 272 && dv == 64) ? 0 : SA_EUNSUPPORTED; }
-
-static void scan_segments(int N, int& S, int& seg_len, const void* ws) {
-    S = ws ? (N + 127) / 128 : 1;      // VALU path: ~128 positions per block
-    if (S > 16) S = 16;
-    if (S < 1) S = 1;
-    seg_len = (N + S - 1) / S;
-    S = (N + seg_len - 1) / seg_len;
+// The scans run on the chunked MFMA kernels only (float4-addressable feature rows, 64 value columns); any other shape is refused, there is no slower path.
+static int check_scan(int B, int N, int G, int LDF, int dv) {
+    return (B > 0 && N > 0 && G > 0 && LDF > 0 && LDF <= 272 && (LDF & 15) == 0 && dv == 64) ? 0 : SA_EUNSUPPORTED;
 }
 
 extern "C" int64_t sa_favor_scan_workspace_bytes(int B, int N, int G, int LDF, int dv) {
     return (int64_t)B * G * ((N + 63) / 64) * LDF * (dv + 1) * 4;  // one state (+ its running column sums) per 64-position chunk
 }
 
-// which == 0: scan A, 1: scan B.  With a workspace: chunked MFMA path (3 launches); without: one VALU block per (b, g).
-template <typename K>
-static int run_scan(K valu_kernel, int which, ScanArgs& s, unsigned base_blocks, float* ws, hipStream_t st) {
-    const bool no_mfma = dbg(SA_DBG_SCAN_VALU);
-    if (!ws) {
-        s.S = 1; s.seg_len = s.N; s.pass = 0; s.state = nullptr;
-        SA_LAUNCH(valu_kernel, dim3(base_blocks), dim3(256), 0, st, s);
-        SA_CHECK_LAUNCH();
-        return 0;
-    }
+// which == 0: scan A, 1: scan B.  Chunk state sums + their exclusive prefix in `ws` (skipped when it already holds them), then the chunk outputs.
+static int run_scan(int which, ScanArgs& s, float* ws, hipStream_t st) {
     s.state = ws;
     const int64_t bg = (int64_t)s.B * s.G;
-    int64_t elems = (int64_t)s.LDF * s.dv;
-    const bool mfma_ok = !no_mfma && (s.LDF & 15) == 0 && s.LDF <= 272 && s.dv == 64;
     if (s.zmode) s.zcol = 1;
-    if ((s.zcol || s.state_ready) && !mfma_ok) return SA_EUNSUPPORTED;   // the fused running sums / shared states exist on the chunked MFMA path only
-    if (mfma_ok) {
-        elems += s.zcol ? s.LDF : 0;
-        s.S = (s.N + 63) / 64;
-        s.seg_len = 64;
-        const unsigned nblk = (unsigned)(bg * s.S);
-        const int exact = (int)((g_debug_flags.load(std::memory_order_relaxed) >> SA_DBG_SCAN_EXACT_SHIFT) & 7u) | (s.exact ? 7 : 0);   // bit 0: state sums, bit 1: scan A outputs, bit 2: scan B outputs on the exact-fp32 MFMA kernels
-        const bool fits32 = (int64_t)s.N * s.G * s.LDF * 4 < ((int64_t)1 << 31) && (int64_t)s.N * std::max(s.b_stride, std::max(s.c_stride, s.y_stride)) * 4 < ((int64_t)1 << 31);
-        if (!s.state_ready) {
-            if (!(exact & 1) && fits32) SA_LAUNCH(favor_chunk_state_split_kernel, dim3(nblk), dim3(256), 0, st, s);
-            else SA_LAUNCH(favor_chunk_state_kernel, dim3(nblk), dim3(256), 0, st, s);
-            SA_CHECK_LAUNCH();
-            SA_LAUNCH(scan_state_prefix_kernel, dim3((unsigned)((bg * elems + 255) / 256)), dim3(256), 0, st, ws, bg, s.S, elems);
-            SA_CHECK_LAUNCH();
-        }
-        if (which == 0) {
-            if (!(exact & 2) && fits32) SA_LAUNCH(favor_chunk_out_a_split_kernel, dim3(nblk), dim3(256), 0, st, s);
-            else SA_LAUNCH(favor_chunk_out_a_kernel, dim3(nblk), dim3(256), 0, st, s);
-        } else {
-            if (!(exact & 4) && fits32) SA_LAUNCH(favor_chunk_out_b_split_kernel, dim3(nblk), dim3(256), 0, st, s);
-            else SA_LAUNCH(favor_chunk_out_b_kernel, dim3(nblk), dim3(256), 0, st, s);
-        }
+    const int64_t elems = (int64_t)s.LDF * s.dv + (s.zcol ? s.LDF : 0);
+    s.S = (s.N + 63) / 64;
+    s.seg_len = 64;
+    const unsigned nblk = (unsigned)(bg * s.S);
+    const int exact = (int)((g_debug_flags.load(std::memory_order_relaxed) >> SA_DBG_SCAN_EXACT_SHIFT) & 7u) | (s.exact ? 7 : 0);   // bit 0: state sums, bit 1: scan A outputs, bit 2: scan B outputs on the exact-fp32 MFMA kernels
+    const bool fits32 = (int64_t)s.N * s.G * s.LDF * 4 < ((int64_t)1 << 31) && (int64_t)s.N * std::max(s.b_stride, std::max(s.c_stride, s.y_stride)) * 4 < ((int64_t)1 << 31);
+    if (!s.state_ready) {
+        if (!(exact & 1) && fits32) SA_LAUNCH(favor_chunk_state_split_kernel, dim3(nblk), dim3(256), 0, st, s);
+        else SA_LAUNCH(favor_chunk_state_kernel, dim3(nblk), dim3(256), 0, st, s);
         SA_CHECK_LAUNCH();
-        return 0;
-    }
-    scan_segments(s.N, s.S, s.seg_len, ws);
-    s.pass = 1;
-    SA_LAUNCH(valu_kernel, dim3(base_blocks * s.S), dim3(256), 0, st, s);
-    SA_CHECK_LAUNCH();
-    SA_LAUNCH(scan_state_prefix_kernel, dim3((unsigned)((bg * elems + 255) / 256)), dim3(256), 0, st, ws, bg, s.S, elems);
-    SA_CHECK_LAUNCH();
-    s.pass = 2;
-    SA_LAUNCH(valu_kernel, dim3(base_blocks * s.S), dim3(256), 0, st, s);
-    SA_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sa_favor_scan_a(const float* a, const float* c, const float* b, int b_stride, int b_off, const float* b_scale, float* y, int y_stride,
-                               int y_off, const float* y_scale, int B, int N, int G, int LDF, int dv, int reverse, int accumulate, float* state_ws,
-                               void* stream) {
-    if (!a || !c || !b || !y) return SA_EINVAL;
-    if (check_scan(B, N, G, LDF, dv)) return SA_EUNSUPPORTED;
-    ScanArgs s = {};
-    s.a = a; s.c_feat = c; s.b = b; s.b_scale = b_scale; s.y = y; s.y_scale = y_scale;
-    s.B = B; s.N = N; s.G = G; s.LDF = LDF; s.dv = dv; s.b_stride = b_stride; s.b_off = b_off; s.y_stride = y_stride; s.y_off = y_off;
-    s.reverse = reverse; s.accumulate = accumulate;
-    return run_scan(favor_scan_a_kernel, 0, s, (unsigned)(B * G * (dv / 16)), state_ws, ST(stream));
-}
-
-extern "C" int sa_favor_scan_b(const float* a, const float* b, int b_stride, int b_off, const float* b_scale, const float* c, int c_stride, int c_off,
-                               const float* c_scale, float* y, const float* ex_scale, const float* ex_vec, float ex_const, int B, int N, int G,
-                               int LDF, int dv, int reverse, float* state_ws, void* stream) {
-    if (!a || !c || !b || !y) return SA_EINVAL;
-    if (check_scan(B, N, G, LDF, dv)) return SA_EUNSUPPORTED;
-    ScanArgs s = {};
-    s.a = a; s.b = b; s.c_col = c; s.b_scale = b_scale; s.c_scale = c_scale; s.y = y; s.ex_scale = ex_scale; s.ex_vec = ex_vec; s.ex_const = ex_const;
-    s.B = B; s.N = N; s.G = G; s.LDF = LDF; s.dv = dv; s.b_stride = b_stride; s.b_off = b_off; s.c_stride = c_stride; s.c_off = c_off; s.reverse = reverse;
-    return run_scan(favor_scan_b_kernel, 1, s, (unsigned)(B * G * ((LDF + 63) / 64)), state_ws, ST(stream));
-}
-
-extern "C" int sa_cumsum_rows(const float* x, const float* scale, float* out, int B, int N, int G, int LDF, int reverse, float* seg_ws, void* stream) {
-    if (!x || !out || B <= 0 || N <= 0 || G <= 0 || LDF <= 0) return SA_EINVAL;
-    int S, seg_len;
-    scan_segments(N, S, seg_len, seg_ws);   // seg_ws: B*G*S*LDF floats (<= 1/dv of the scan workspace)
-    const int64_t threads = (int64_t)B * G * LDF * S;
-    const unsigned nblk = (unsigned)((threads + 255) / 256);
-    if (S > 1) {
-        SA_LAUNCH(cumsum_rows_kernel, dim3(nblk), dim3(256), 0, ST(stream), x, scale, (float*)nullptr, seg_ws, B, N, G, LDF, reverse, S, seg_len);
+        SA_LAUNCH(scan_state_prefix_kernel, dim3((unsigned)((bg * elems + 255) / 256)), dim3(256), 0, st, ws, bg, s.S, elems);
         SA_CHECK_LAUNCH();
     }
-    SA_LAUNCH(cumsum_rows_kernel, dim3(nblk), dim3(256), 0, ST(stream), x, scale, out, S > 1 ? seg_ws : (float*)nullptr, B, N, G, LDF, reverse, S, seg_len);
-    SA_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sa_favor_den(const float* q, const float* z, float eps, float* inv, int64_t rows, int m, int LDF, void* stream) {
-    if (!q || !z || !inv || rows <= 0) return SA_EINVAL;
-    SA_LAUNCH(favor_den_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST(stream), q, z, eps, inv, rows, m, LDF);
+    if (which == 0) {
+        if (!(exact & 2) && fits32) SA_LAUNCH(favor_chunk_out_a_split_kernel, dim3(nblk), dim3(256), 0, st, s);
+        else SA_LAUNCH(favor_chunk_out_a_kernel, dim3(nblk), dim3(256), 0, st, s);
+    } else {
+        if (!(exact & 4) && fits32) SA_LAUNCH(favor_chunk_out_b_split_kernel, dim3(nblk), dim3(256), 0, st, s);
+        else SA_LAUNCH(favor_chunk_out_b_kernel, dim3(nblk), dim3(256), 0, st, s);
+    }
     SA_CHECK_LAUNCH();
     return 0;
 }
@@ -2605,8 +2369,8 @@ extern "C" int sa_gemv_rows(const float* x, int x_stride, int in, int B, int nse
 }
 
 // scan A with the FAVOR+ normaliser fused: y_i = (sum_{j<=i} (c_i . a_j) b_j) / (c_i . (sum_{j<=i} a_j + den_eps)); inv_out[i] = 1 / that
-// denominator (kept for the backward pass).  Replaces sa_cumsum_rows + sa_favor_den + sa_favor_scan_a(y_scale = inv).  Chunked MFMA
-// path only (LDF % 16 == 0, LDF <= 272, dv == 64, workspace given): SA_EUNSUPPORTED otherwise.
+// denominator (kept for the backward pass): the running key sums ride along as the extra state column, no separate prefix-sum / normaliser
+// pass.  LDF % 16 == 0, LDF <= 272, dv == 64, workspace given: SA_EUNSUPPORTED otherwise (as for every scan below).
 extern "C" int sa_favor_scan_a_norm(const float* a, const float* c, const float* b, int b_stride, int b_off, float* y, int y_stride, int y_off, float* inv_out,
                                     float den_eps, int B, int N, int G, int LDF, int dv, float* state_ws, int state_flags, void* stream) {
     if (!a || !c || !b || !y || !inv_out || !state_ws) return SA_EINVAL;
@@ -2615,13 +2379,13 @@ extern "C" int sa_favor_scan_a_norm(const float* a, const float* c, const float*
     s.a = a; s.c_feat = c; s.b = b; s.y = y;
     s.B = B; s.N = N; s.G = G; s.LDF = LDF; s.dv = dv; s.b_stride = b_stride; s.b_off = b_off; s.y_stride = y_stride; s.y_off = y_off;
     s.zmode = 1; s.den_eps = den_eps; s.inv_out = inv_out; s.state_ready = state_flags & 1; s.exact = (state_flags >> 2) & 1;
-    return run_scan(favor_scan_a_kernel, 0, s, (unsigned)(B * G * (dv / 16)), state_ws, ST(stream));
+    return run_scan(0, s, state_ws, ST(stream));
 }
 
 // scan B with a cumulative extra term computed on the fly (no cumsum pass, no [B,N,G,LDF] operand):
 //   ex_mode 1: y_i[m] += ex_scale_i * (sum_{j<=i} a_j[m] + ex_const)      (gradient wrt the query features: ex_scale = d den)
 //   ex_mode 2: y_i[m] += sum_{j<=i} a_j[m] ex_scale_j                     (gradient wrt the key features, reversed scan)
-// (j <= i in scan order).  Chunked MFMA path only.
+// (j <= i in scan order).
 extern "C" int sa_favor_scan_b_cum(const float* a, const float* b, int b_stride, int b_off, const float* b_scale, const float* c, int c_stride, int c_off,
                                    const float* c_scale, float* y, const float* ex_scale, int ex_mode, float ex_const, int B, int N, int G, int LDF, int dv,
                                    int reverse, float* state_ws, int state_flags, void* stream) {
@@ -2631,12 +2395,12 @@ extern "C" int sa_favor_scan_b_cum(const float* a, const float* b, int b_stride,
     s.a = a; s.b = b; s.c_col = c; s.b_scale = b_scale; s.c_scale = c_scale; s.y = y; s.ex_scale = ex_scale; s.ex_vec = nullptr; s.ex_const = ex_const;
     s.B = B; s.N = N; s.G = G; s.LDF = LDF; s.dv = dv; s.b_stride = b_stride; s.b_off = b_off; s.c_stride = c_stride; s.c_off = c_off; s.reverse = reverse;
     s.zmode = ex_mode; s.state_ready = state_flags & 1; s.exact = (state_flags >> 2) & 1;
-    return run_scan(favor_scan_b_kernel, 1, s, (unsigned)(B * G * ((LDF + 63) / 64)), state_ws, ST(stream));
+    return run_scan(1, s, state_ws, ST(stream));
 }
 
-// sa_favor_scan_a on a state buffer some other scan of the SAME (a, b, b_scale, reverse) already filled: state_flags bit 0 = the exclusive
-// chunk prefixes are in state_ws (skip the state and prefix passes), bit 1 = the buffer has the extra running-sum column (it was written
-// by sa_favor_scan_a_norm / sa_favor_scan_b_cum).  The three backward scans of a FAVOR+ head need two distinct state sets, not four.
+// plain scan A (y_i = y_scale_i sum_{j<=i} (c_i . a_j) b_j b_scale_j), optionally on a state buffer some other scan of the SAME
+// (a, b, b_scale, reverse) already filled: state_flags bit 0 = the exclusive chunk prefixes are in state_ws (skip the state and prefix
+// passes), bit 1 = the buffer has the extra running-sum column (it was written by sa_favor_scan_a_norm / sa_favor_scan_b_cum).  The three backward scans of a FAVOR+ head need two distinct state sets, not four.
 extern "C" int sa_favor_scan_a_state(const float* a, const float* c, const float* b, int b_stride, int b_off, const float* b_scale, float* y, int y_stride,
                                      int y_off, const float* y_scale, int B, int N, int G, int LDF, int dv, int reverse, int accumulate, float* state_ws,
                                      int state_flags, void* stream) {
@@ -2649,5 +2413,5 @@ extern "C" int sa_favor_scan_a_state(const float* a, const float* c, const float
     s.state_ready = state_flags & 1;
     s.zcol = (state_flags >> 1) & 1;
     s.exact = (state_flags >> 2) & 1;
-    return run_scan(favor_scan_a_kernel, 0, s, (unsigned)(B * G * (dv / 16)), state_ws, ST(stream));
+    return run_scan(0, s, state_ws, ST(stream));
 }

@@ -383,8 +383,6 @@ class PackSet:
         self._blocks = 0
 
     def repack(self, ops: Sequence["ConvOp"]):
-        if debug.host("no_batched_pack"):
-            return
         items = [(op, key, ent) for op in ops for key, ent in op._packs.items() if ent[0].device == op.weight.device]
         if not items:
             return

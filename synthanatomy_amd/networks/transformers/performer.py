@@ -523,7 +523,7 @@ class _LayerEngine:
         return self._rot[1], self._rot[2]
 
     def _scan_ws(self, B, N, G, dev):
-        """scratch for the segment-parallel scans (states of <= 16 segments per (batch, head)); reused by every call of this layer"""
+        """scratch for the chunked scans (one state per 64-position chunk of every (batch, head)); reused by every call of this layer"""
         n = _ffi.lib().sa_favor_scan_workspace_bytes(B, N, G, self.LDF, self.dh) // 4
         if self._ws is None or self._ws.numel() < n or self._ws.device != dev:
             self._ws = torch.empty(n, dtype=torch.float32, device=dev)
@@ -571,97 +571,31 @@ class _LayerEngine:
         qs = q.stride(0)   # row stride of q / k / v (3 * inner when they are column blocks of one matrix)
         self._rotate_global(q, k, B, N, 0)       # (rotary_position_emb=True only; the tape keeps the rotated rows -- what the FAVOR+ backward differentiates)
         attn = torch.empty(R, inner, dtype=f32, device=dev)
+        fused = G > 0 and self._fused_favor()
         # throughput mode: the attention kernels write the bf16 operand of to_out next to the fp32 rows (no cast launch); needs every head on a kernel that can
-        attn_lp = (torch.empty(R, inner, dtype=T, device=dev)
-                   if (T == torch.bfloat16 and (G == 0 or self._fused_favor()) and not debug.host("no_lp_mirrors")) else None)
+        attn_lp = torch.empty(R, inner, dtype=T, device=dev) if (T == torch.bfloat16 and (G == 0 or fused)) else None
         sv = dict(x=x, xa=xa, xaT=xaT, st_a=st_a, q=q, k=k, v=v, attn=attn, seed=seed)
         # throughput mode with both kinds of heads: the local-window heads' blocks ride in the FAVOR+ launches (sa_local_attn_args): rotary first, no launch of their own
         # (not with attn_dropout: the co-launched bodies carry no dropout, the local heads run the sa_local_attn_fwd_dropout launch below)
         la_args = None
-        if G > 0 and L > 0 and self._fused_favor() and not debug.host("no_attn_colaunch") and not pa:
+        if fused and L > 0 and not pa:
             la_args = self._local_fwd_prep(q, k, v, qs, attn, attn_lp, B, N, R, dev, sv)
-        if G > 0 and self._fused_favor():
-            tiles, ps = self._proj_tiles()
-            offq = torch.empty(R * G, dtype=f32, device=dev)
-            offk = torch.empty(R * G, dtype=f32, device=dev)
-            amq = torch.empty(R * G, dtype=torch.int32, device=dev)
-            gws = torch.empty(1, dtype=torch.int64, device=dev)
-            inv = torch.empty(R * G, dtype=f32, device=dev)
-            nst = lib.sa_favor_fused_state_bytes(B, N, G, m) // 4
-            if tape is not None:     # training: the chunk prefixes (sum k' (x) v | sum k') are kept for the dq' scan of the backward pass
-                state = torch.empty(nst, dtype=f32, device=dev)
-            else:
-                if self._ws is None or self._ws.numel() < nst or self._ws.device != dev:
-                    self._ws = torch.empty(nst, dtype=f32, device=dev)
-                state = self._ws
-            t0 = _favor_bracket_begin()
-            _ck(lib.sa_favor_fused_prepass(_ffi.ptr(q), _ffi.ptr(k), qs, G, _ffi.ptr(tiles), _ffi.ptr(offq), _ffi.ptr(amq), _ffi.ptr(offk), _ffi.ptr(gws), R * G, m, dh, st),
-                "sa_favor_fused_prepass")
-            rc = lib.sa_favor_fused_fwd(_ffi.ptr(q), _ffi.ptr(k), _ffi.ptr(v), qs, _ffi.ptr(tiles), _ffi.ptr(ps), _ffi.ptr(offq), _ffi.ptr(offk), _ffi.ptr(gws),
-                                        _ffi.ptr(attn), inner, _ffi.ptr(inv), 1e-6, B, N, G, m, _ffi.ptr(state), _ffi.ptr(attn_lp),
-                                        ctypes.byref(la_args) if la_args is not None else None, st)
-            if rc == _ffi.SA_EUNSUPPORTED and la_args is not None:      # (exact-fp32 local attention: its kernels cannot share the launch) -> separate launches
-                la_args = None
-                rc = lib.sa_favor_fused_fwd(_ffi.ptr(q), _ffi.ptr(k), _ffi.ptr(v), qs, _ffi.ptr(tiles), _ffi.ptr(ps), _ffi.ptr(offq), _ffi.ptr(offk), _ffi.ptr(gws),
-                                            _ffi.ptr(attn), inner, _ffi.ptr(inv), 1e-6, B, N, G, m, _ffi.ptr(state), _ffi.ptr(attn_lp), None, st)
-            _ck(rc, "sa_favor_fused_fwd")
-            _favor_bracket_end(t0, "favor_prepass+fstates+fout_a" + ("_la" if la_args is not None else ""), B * N * G * FAVOR_FWD_FLOP_PER_HEAD_ROW(m, dh))
-            sv.update(fused=True, offq=offq, offk=offk, amq=amq, gws=gws, inv=inv, scan_state=state if tape is not None else None)
+        if fused:
+            la_args = self._favor_fused_fwd(q, k, v, qs, attn, attn_lp, la_args, B, N, tape, sv)
         elif G > 0:
-            pop = self._proj_op()
-            if self._xf:   # fp32 parity mode: exact-fp32 GEMM on contiguous copies of the global-head columns
-                qg = q[:, : G * dh].contiguous()
-                kg = k[:, : G * dh].contiguous()
-                sst = G * dh
-                ddq = pop.fprop(qg.view(1, 1, 1, R * G, dh), out_channels_stride=LDF, use_bias=False).view(R * G, LDF)
-                ddk = pop.fprop(kg.view(1, 1, 1, R * G, dh), out_channels_stride=LDF, use_bias=False).view(R * G, LDF)
-            else:          # throughput mode: HBM-bound split-bf16 projection kernels reading the head blocks of q / k in place
-                qg, kg, sst = q, k, qs
-                ps = self._pop[2]
-                ddq = torch.empty(R * G, LDF, dtype=f32, device=dev)
-                ddk = torch.empty(R * G, LDF, dtype=f32, device=dev)
-            qf, kf = torch.empty_like(ddq), torch.empty_like(ddk)
-            gws = torch.empty(2, dtype=torch.int64, device=dev)
-            kmode = 0      # the keys' feature map finds the global maximum itself ...
-            if not self._xf:
-                # queries: projection and feature map in one launch (the row maximum is local to the block)
-                _ck(lib.sa_favor_project_features(_ffi.ptr(q), qs, G, _ffi.ptr(ps), _ffi.ptr(ddq), _ffi.ptr(qf), R * G, m, LDF, dh, st), "sa_favor_project_features(q)")
-                _ck(lib.sa_favor_project(_ffi.ptr(k), qs, G, _ffi.ptr(ps), _ffi.ptr(ddk), _ffi.ptr(gws), R * G, m, LDF, dh, st), "sa_favor_project(k)")
-                kmode = 2  # ... unless the projection kernel already left it in gws (from its accumulators: no extra pass over ddk)
-            else:
-                _ck(lib.sa_favor_features_fwd(_ffi.ptr(ddq), _ffi.ptr(qg), sst, 0, G, dh, 1, _ffi.ptr(qf), None, R * G, m, LDF, st), "favor_features(q)")
-            _ck(lib.sa_favor_features_fwd(_ffi.ptr(ddk), _ffi.ptr(kg), sst, 0, G, dh, kmode, _ffi.ptr(kf), _ffi.ptr(gws), R * G, m, LDF, st), "favor_features(k)")
-            ws = self._scan_ws(B, N, G, dev)
-            if tape is not None and (not debug.host("no_fused_sums")):   # training: the chunk states (sum k' (x) v, sum k') are kept for the dq' scan of the backward pass
-                ws = torch.empty_like(ws)
-            inv = torch.empty(R * G, dtype=f32, device=dev)
-            Z = None
-            # normaliser fused into the scan (the running key sums ride along as an extra state column): no cumsum / den passes
-            rc = lib.sa_favor_scan_a_norm(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dh,
-                                          _ffi.ptr(ws), self._xf, st) if (not debug.host("no_fused_sums")) else _ffi.SA_EUNSUPPORTED
-            if rc == _ffi.SA_EUNSUPPORTED:
-                Z = torch.empty_like(kf)
-                _ck(lib.sa_cumsum_rows(_ffi.ptr(kf), None, _ffi.ptr(Z), B, N, G, LDF, 0, _ffi.ptr(ws), st), "sa_cumsum_rows")
-                _ck(lib.sa_favor_den(_ffi.ptr(qf), _ffi.ptr(Z), 1e-6, _ffi.ptr(inv), R * G, m, LDF, st), "sa_favor_den")
-                _ck(lib.sa_favor_scan_a(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), B, N, G, LDF, dh, 0, 0,
-                                        _ffi.ptr(ws), st), "sa_favor_scan_a")
-            else:
-                _ck(rc, "sa_favor_scan_a_norm")
-            sv.update(qg=qg, kg=kg, ddq=ddq, ddk=ddk, qf=qf, kf=kf, gws=gws, Z=Z, inv=inv, scan_state=ws if (Z is None and tape is not None) else None)
+            self._favor_chunked_fwd(q, k, v, qs, attn, B, N, tape, sv)
         if L > 0 and "lse" not in sv:          # (not prepared for the co-launch)
             self._local_fwd_prep(q, k, v, qs, attn, attn_lp, B, N, R, dev, sv)
-        if L > 0 and la_args is None and pa:
+        if L > 0 and la_args is None:
             qr, kr, lse = sv["qr"], sv["kr"], sv["lse"]
-            _ck(lib.sa_local_attn_fwd_dropout(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh,
-                                              _ffi.ptr(lse), B, N, L, self.W, dh, _ffi.ptr(attn_lp), pa, seed, self.site + 2, st), "sa_local_attn_fwd_dropout")
-        elif L > 0 and la_args is None:
-            qr, kr, lse = sv["qr"], sv["kr"], sv["lse"]
-            _ck(lib.sa_local_attn_fwd(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh, _ffi.ptr(lse),
-                                      B, N, L, self.W, dh, _ffi.ptr(attn_lp), st), "sa_local_attn_fwd")
+            if pa:
+                _ck(lib.sa_local_attn_fwd_dropout(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh,
+                                                  _ffi.ptr(lse), B, N, L, self.W, dh, _ffi.ptr(attn_lp), pa, seed, self.site + 2, st), "sa_local_attn_fwd_dropout")
+            else:
+                _ck(lib.sa_local_attn_fwd(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh, _ffi.ptr(lse),
+                                          B, N, L, self.W, dh, _ffi.ptr(attn_lp), st), "sa_local_attn_fwd")
         attnT = attn_lp if attn_lp is not None else _cast(attn, T)
         ga = self._gate(self.aw, dev)
-        gf = self._gate(self.fw, dev)
-        fuse_epi = lp and not debug.host("no_fused_epilogues")
         if pa:
             # attn_dropout: F' = dropout(to_out(attn)) and x1 = x + g F' (+ its bf16 copy) in one launch after the plain to_out GEMM; F' is what the gate gradient reads
             Fa = self.ops["to_out"].fprop(_as5(attnT)).view(R, self.dim)
@@ -669,43 +603,107 @@ class _LayerEngine:
             x1T = torch.empty(x.shape, dtype=T, device=dev) if lp else None
             _ck(lib.sa_dropout_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), _ffi.ptr(x1T), _ffi.dtype_id(T) if lp else 0,
                                           x.numel(), pa, seed, self.site + 1, st), "sa_dropout_rezero_fwd")
-        elif fuse_epi:
+        elif lp:
             # throughput mode: x1 = x + g F leaves the to_out launch itself (fp32 residual stream + its bf16 copy for the next dense layer + the branch
             # output F the ReZero backward needs) -- no sa_rezero_fwd launch, F is never re-read
             x1, Fa, x1T = self.ops["to_out"].fprop(_as5(attnT), out_dtype=f32, alpha=ga, addend=_as5(x), want_pre=True, want_lp=True)
             x1, Fa, x1T = x1.view(R, self.dim), Fa.view(R, self.dim), x1T.view(R, self.dim)
-        else:
+        else:       # LayerNorm / fp32: the residual as a launch of its own, no low-precision copy
             Fa = self.ops["to_out"].fprop(_as5(attnT)).view(R, self.dim)
-            x1 = torch.empty_like(x)
-            x1T = torch.empty(x.shape, dtype=T, device=dev) if lp else None
-            _ck(lib.sa_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), _ffi.ptr(x1T), _ffi.dtype_id(T) if lp else 0, x.numel(), st),
-                "sa_rezero_fwd")
+            x1, x1T = torch.empty_like(x), None
+            _ck(lib.sa_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), None, 0, x.numel(), st), "sa_rezero_fwd")
+        gf = self._gate(self.fw, dev)
         xf, st_f = self._pre(self.fw, x1, R)
         xfT = x1T if lp else _cast(xf, T)
-        if fuse_epi:
+        if lp:
             # h = gelu(u) and the pre-activation u (for the GELU backward) from ONE launch; x2 = x1 + g F from the w2 launch
             h, u, _ = self.ops["w1"].fprop(_as5(xfT), act=_ffi.ACT_GELU, want_pre=True)
             h, u = h.view(R, -1), u.view(R, -1)
             if pf:   # ff_dropout: h *= keep / (1 - p) in place, between the GELU and w2 (u stays the undropped pre-activation)
                 _ck(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
             x2, Ff, x2T = self.ops["w2"].fprop(_as5(h), out_dtype=f32, alpha=gf, addend=_as5(x1), want_pre=True, want_lp=True)
-            x2, Ff, x2T = x2.view(R, self.dim), Ff.view(R, self.dim), x2T.view(R, self.dim)
-        else:
+            x2, Ff, self.out_lp = x2.view(R, self.dim), Ff.view(R, self.dim), x2T.view(R, self.dim)
+        else:       # LayerNorm / fp32: GELU and the residual as launches of their own
             u = self.ops["w1"].fprop(_as5(xfT)).view(R, -1)
             h = torch.empty_like(u)
             _ck(lib.sa_gelu(_ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(h), _ffi.dtype_id(h.dtype), u.numel(), st), "sa_gelu")
             if pf:
                 _ck(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
             Ff = self.ops["w2"].fprop(_as5(h)).view(R, self.dim)
-            x2 = torch.empty_like(x)
-            x2T = torch.empty(x.shape, dtype=T, device=dev) if lp else None
-            _ck(lib.sa_rezero_fwd(_ffi.ptr(x1), _ffi.ptr(Ff), _ffi.dtype_id(Ff.dtype), _ffi.ptr(gf), _ffi.ptr(x2), _ffi.ptr(x2T), _ffi.dtype_id(T) if lp else 0, x.numel(), st),
-                "sa_rezero_fwd")
-        self.out_lp = x2T
+            x2, self.out_lp = torch.empty_like(x), None
+            _ck(lib.sa_rezero_fwd(_ffi.ptr(x1), _ffi.ptr(Ff), _ffi.dtype_id(Ff.dtype), _ffi.ptr(gf), _ffi.ptr(x2), None, 0, x.numel(), st), "sa_rezero_fwd")
         if tape is not None:
             sv.update(attnT=attnT, Fa=Fa, x1=x1, xf=xf, xfT=xfT, st_f=st_f, u=u, h=h, Ff=Ff)
             tape.append(sv)
         return x2
+
+    def _favor_fused_fwd(self, q, k, v, qs, attn, attn_lp, la_args, B, N, tape, sv):
+        """FAVOR+ heads, fused route (throughput mode, csrc/favor_fused.hip): prepass + one forward call; returns la_args when the local heads rode along"""
+        lib, st, dev, f32 = _ffi.lib(), _ffi.stream(), q.device, torch.float32
+        R, G, dh, m, inner = B * N, self.G, self.dh, self.m, self.H * self.dh
+        tiles, ps = self._proj_tiles()
+        offq, offk, inv = (torch.empty(R * G, dtype=f32, device=dev) for _ in range(3))
+        amq = torch.empty(R * G, dtype=torch.int32, device=dev)
+        gws = torch.empty(1, dtype=torch.int64, device=dev)
+        nst = lib.sa_favor_fused_state_bytes(B, N, G, m) // 4
+        if tape is not None:     # training: the chunk prefixes (sum k' (x) v | sum k') are kept for the dq' scan of the backward pass
+            state = torch.empty(nst, dtype=f32, device=dev)
+        else:
+            if self._ws is None or self._ws.numel() < nst or self._ws.device != dev:
+                self._ws = torch.empty(nst, dtype=f32, device=dev)
+            state = self._ws
+
+        def favor_fwd(la):
+            return lib.sa_favor_fused_fwd(_ffi.ptr(q), _ffi.ptr(k), _ffi.ptr(v), qs, _ffi.ptr(tiles), _ffi.ptr(ps), _ffi.ptr(offq), _ffi.ptr(offk), _ffi.ptr(gws),
+                                          _ffi.ptr(attn), inner, _ffi.ptr(inv), 1e-6, B, N, G, m, _ffi.ptr(state), _ffi.ptr(attn_lp),
+                                          ctypes.byref(la) if la is not None else None, st)
+        t0 = _favor_bracket_begin()
+        _ck(lib.sa_favor_fused_prepass(_ffi.ptr(q), _ffi.ptr(k), qs, G, _ffi.ptr(tiles), _ffi.ptr(offq), _ffi.ptr(amq), _ffi.ptr(offk), _ffi.ptr(gws), R * G, m, dh, st),
+            "sa_favor_fused_prepass")
+        rc = favor_fwd(la_args)
+        if rc == _ffi.SA_EUNSUPPORTED and la_args is not None:      # (exact-fp32 local attention: its kernels cannot share the launch) -> separate launches
+            la_args = None
+            rc = favor_fwd(None)
+        _ck(rc, "sa_favor_fused_fwd")
+        _favor_bracket_end(t0, "favor_prepass+fstates+fout_a" + ("_la" if la_args is not None else ""), B * N * G * FAVOR_FWD_FLOP_PER_HEAD_ROW(m, dh))
+        sv.update(fused=True, offq=offq, offk=offk, amq=amq, gws=gws, inv=inv, scan_state=state if tape is not None else None)
+        return la_args
+
+    def _favor_chunked_fwd(self, q, k, v, qs, attn, B, N, tape, sv):
+        """FAVOR+ heads, chunked route (fp32 parity mode, no_fused_favor): projection -> feature maps in HBM -> causal scan with the normaliser fused"""
+        lib, st, dev, f32 = _ffi.lib(), _ffi.stream(), q.device, torch.float32
+        R, G, dh, m, LDF, inner = B * N, self.G, self.dh, self.m, self.LDF, self.H * self.dh
+        pop = self._proj_op()
+        if self._xf:   # fp32 parity mode: exact-fp32 GEMM on contiguous copies of the global-head columns
+            qg = q[:, : G * dh].contiguous()
+            kg = k[:, : G * dh].contiguous()
+            sst = G * dh
+            ddq = pop.fprop(qg.view(1, 1, 1, R * G, dh), out_channels_stride=LDF, use_bias=False).view(R * G, LDF)
+            ddk = pop.fprop(kg.view(1, 1, 1, R * G, dh), out_channels_stride=LDF, use_bias=False).view(R * G, LDF)
+        else:          # throughput mode: HBM-bound split-bf16 projection kernels reading the head blocks of q / k in place
+            qg, kg, sst = q, k, qs
+            ps = self._pop[2]
+            ddq = torch.empty(R * G, LDF, dtype=f32, device=dev)
+            ddk = torch.empty(R * G, LDF, dtype=f32, device=dev)
+        qf, kf = torch.empty_like(ddq), torch.empty_like(ddk)
+        gws = torch.empty(2, dtype=torch.int64, device=dev)
+        kmode = 0      # the keys' feature map finds the global maximum itself ...
+        if not self._xf:
+            # queries: projection and feature map in one launch (the row maximum is local to the block)
+            _ck(lib.sa_favor_project_features(_ffi.ptr(q), qs, G, _ffi.ptr(ps), _ffi.ptr(ddq), _ffi.ptr(qf), R * G, m, LDF, dh, st), "sa_favor_project_features(q)")
+            _ck(lib.sa_favor_project(_ffi.ptr(k), qs, G, _ffi.ptr(ps), _ffi.ptr(ddk), _ffi.ptr(gws), R * G, m, LDF, dh, st), "sa_favor_project(k)")
+            kmode = 2  # ... unless the projection kernel already left it in gws (from its accumulators: no extra pass over ddk)
+        else:
+            _ck(lib.sa_favor_features_fwd(_ffi.ptr(ddq), _ffi.ptr(qg), sst, 0, G, dh, 1, _ffi.ptr(qf), None, R * G, m, LDF, st), "favor_features(q)")
+        _ck(lib.sa_favor_features_fwd(_ffi.ptr(ddk), _ffi.ptr(kg), sst, 0, G, dh, kmode, _ffi.ptr(kf), _ffi.ptr(gws), R * G, m, LDF, st), "favor_features(k)")
+        ws = self._scan_ws(B, N, G, dev)
+        if tape is not None:   # training: the chunk states (sum k' (x) v, sum k') are kept for the dq' scan of the backward pass
+            ws = torch.empty_like(ws)
+        inv = torch.empty(R * G, dtype=f32, device=dev)
+        # the running key sums ride along as an extra state column of the scan, which divides by the normaliser itself
+        _ck(lib.sa_favor_scan_a_norm(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dh,
+                                     _ffi.ptr(ws), self._xf, st), "sa_favor_scan_a_norm")
+        sv.update(qg=qg, kg=kg, ddq=ddq, ddk=ddk, qf=qf, kf=kf, gws=gws, inv=inv, scan_state=ws if tape is not None else None)
 
     # ---------------------------------------------------------------------------------------------- stateful decoding (one position)
     def _local_fwd_prep(self, q, k, v, qs, attn, attn_lp, B, N, R, dev, sv):
@@ -725,10 +723,16 @@ class _LayerEngine:
             _ck(lib.sa_rotary(_ffi.ptr(k), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(kr), L * dh, 0, N, R, 0, 0, st), "sa_rotary(k)")
         lse = torch.empty(R * L, dtype=f32, device=dev)
         sv.update(qr=qr, kr=kr, lse=lse)
-        a = _ffi.LocalAttnArgs()
-        a.q, a.k, a.v = qr.data_ptr(), kr.data_ptr(), v.data_ptr()
-        a.q_stride, a.q_off, a.k_stride, a.k_off, a.v_stride, a.v_off, a.o_stride, a.o_off = L * dh, 0, L * dh, 0, qs, G * dh, inner, G * dh
+        a = self._local_args(sv, v, qs)
         a.o, a.lse, a.o_lp = attn.data_ptr(), lse.data_ptr(), (attn_lp.data_ptr() if attn_lp is not None else None)
+        return a
+
+    def _local_args(self, sv, v, qs):
+        """sa_local_attn_args with what both passes address alike: rotated q | k, v and the local heads' column block of the attention rows"""
+        G, L, dh = self.G, self.L, self.dh
+        a = _ffi.LocalAttnArgs()
+        a.q, a.k, a.v = sv["qr"].data_ptr(), sv["kr"].data_ptr(), v.data_ptr()
+        a.q_stride, a.q_off, a.k_stride, a.k_off, a.v_stride, a.v_off, a.o_stride, a.o_off = L * dh, 0, L * dh, 0, qs, G * dh, self.H * dh, G * dh
         a.L, a.W = L, self.W
         return a
 
@@ -764,7 +768,7 @@ class _LayerEngine:
         rnd = 1 if self.dtype == torch.bfloat16 else 0
         rw = rnd
         ws = [m.weight for m in mods]
-        if rnd and not debug.host("no_decode_bf16_weights"):
+        if rnd:
             # bf16 compute: the decode step streams bf16 COPIES of the parameters (the values the kernel would round to anyway): half the bytes per token, and the
             # 200 MB of a 24-layer network stay resident in the 256 MB Infinity Cache between tokens.  Made on first use per parameter version (outside graph capture:
             # the sampler's warm-up step runs first).
@@ -799,7 +803,7 @@ class _LayerEngine:
         qkv = torch.empty(B, 3 * inner, dtype=f32, device=dev)
         self._gemv(xa, [sa.to_q, sa.to_k, sa.to_v], qkv)
         attn = torch.empty(B, inner, dtype=f32, device=dev)
-        merged = G > 0 and L > 0 and dh == 64 and (2 * self.W + 3) // 4 <= 256 and not debug.host("no_attn_step_merge")
+        merged = G > 0 and L > 0 and dh == 64 and (2 * self.W + 3) // 4 <= 256
         if merged:
             # both kinds of heads in TWO launches: [projections | local heads over four key segments], [FAVOR+ update | combine of the segments]
             self._proj_op()
@@ -882,10 +886,92 @@ class _LayerEngine:
         _ck(lib.sa_axpy(_ffi.ptr(dx), _ffi.ptr(dres), 1.0, dx.numel(), st), "sa_axpy")
         return dx
 
+    def _favor_fused_bwd(self, sv, dattn, dq, dk, dv, dq_lp, dk_lp, dv_lp, B, N, pa):
+        """FAVOR+ heads, fused route: one backward call into the global-head columns of dq | dk | dv (and their bf16 mirrors).  When the local-window heads
+        rode along, returns their dq | dk in ROTATED space (the caller rotates them back), else None."""
+        lib, st, dev, f32 = _ffi.lib(), _ffi.stream(), dattn.device, torch.float32
+        R, G, L, dh, m, inner = B * N, self.G, self.L, self.dh, self.m, self.H * self.dh
+        q, k, v, attn = sv["q"], sv["k"], sv["v"], sv["attn"]
+        qs = dq.stride(0)
+        tiles, ps = self._proj_tiles()
+        nst = lib.sa_favor_fused_state_bytes(B, N, G, m) // 4
+        if self._ws is None or self._ws.numel() < nst or self._ws.device != dev:
+            self._ws = torch.empty(nst, dtype=f32, device=dev)
+        dden = torch.empty(R * G, dtype=f32, device=dev)
+        tsum = torch.empty(B * G * ((N + 63) // 64), dtype=f32, device=dev)
+        la_args = dqkr = None
+        if L > 0 and sv.get("scan_state") is not None and not pa:
+            # the local-window heads' backward blocks ride in the FAVOR+ launches (as in the forward pass)
+            dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
+            Db = torch.empty(R * L, dtype=f32, device=dev)
+            la_args = self._local_args(sv, v, qs)
+            la_args.out, la_args.dout, la_args.lse_in = attn.data_ptr(), dattn.data_ptr(), sv["lse"].data_ptr()
+            la_args.dq, la_args.dk, la_args.dv, la_args.Dbuf = dqkr[0].data_ptr(), dqkr[1].data_ptr(), dv.data_ptr(), Db.data_ptr()
+            la_args.dv_lp = dv_lp.data_ptr() if dv_lp is not None else None
+
+        def favor_bwd(la):
+            return lib.sa_favor_fused_bwd(_ffi.ptr(q), _ffi.ptr(k), _ffi.ptr(v), qs, _ffi.ptr(tiles), _ffi.ptr(ps), _ffi.ptr(sv["offq"]), _ffi.ptr(sv["amq"]),
+                                          _ffi.ptr(sv["offk"]), _ffi.ptr(sv["gws"]), _ffi.ptr(dattn), _ffi.ptr(attn), inner, _ffi.ptr(sv["inv"]), _ffi.ptr(dq),
+                                          _ffi.ptr(dk), _ffi.ptr(dv), B, N, G, m, _ffi.ptr(sv.get("scan_state")), _ffi.ptr(self._ws), _ffi.ptr(dden), _ffi.ptr(tsum),
+                                          _ffi.ptr(dq_lp), _ffi.ptr(dk_lp), _ffi.ptr(dv_lp), ctypes.byref(la) if la is not None else None, st)
+        t0 = _favor_bracket_begin()
+        rc = favor_bwd(la_args)
+        if rc == _ffi.SA_EUNSUPPORTED and la_args is not None:   # exact-fp32 local attention / unpaired launches: separate launches in the caller
+            la_args = dqkr = None
+            rc = favor_bwd(None)
+        _ck(rc, "sa_favor_fused_bwd")
+        _favor_bracket_end(t0, "favor_fdden+fpair_states_b+fpair_b_a+fkey_fix" + ("_la" if la_args is not None else ""),
+                           2.0 * B * N * G * FAVOR_FWD_FLOP_PER_HEAD_ROW(m, dh))
+        sv["scan_state"] = None
+        return dqkr
+
+    def _favor_chunked_bwd(self, sv, dattn, dq, dk, dv, B, N):
+        """FAVOR+ heads, chunked route: d den, the three causal scans (dq', dk', dv; the cumulative terms are rebuilt inside them), then the feature-map and
+        projection adjoints into the global-head columns of dq | dk"""
+        lib, st, dev, f32 = _ffi.lib(), _ffi.stream(), dattn.device, torch.float32
+        R, G, dh, m, LDF, inner = B * N, self.G, self.dh, self.m, self.LDF, self.H * self.dh
+        v, attn, qf, kf, inv = sv["v"], sv["attn"], sv["qf"], sv["kf"], sv["inv"]
+        qs = dq.stride(0)
+        dden = torch.empty(R * G, dtype=f32, device=dev)
+        _ck(lib.sa_favor_dden(_ffi.ptr(dattn), _ffi.ptr(attn), inner, 0, G, dh, _ffi.ptr(inv), _ffi.ptr(dden), R * G, st), "sa_favor_dden")
+        ws = self._scan_ws(B, N, G, dev)
+        dqf, dkf = torch.empty_like(qf), torch.empty_like(kf)
+        kept = sv.get("scan_state")   # the forward's chunk states: same (a = k', b = v) -> no state / prefix passes for dq'
+        _ck(lib.sa_favor_scan_b_cum(_ffi.ptr(kf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dqf), _ffi.ptr(dden), 1, 1e-6,
+                                    B, N, G, LDF, dh, 0, _ffi.ptr(kept if kept is not None else ws), (1 if kept is not None else 0) | self._xf, st),
+            "sa_favor_scan_b_cum(dq')")
+        sv["scan_state"] = None
+        _ck(lib.sa_favor_scan_b_cum(_ffi.ptr(qf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dkf), _ffi.ptr(dden), 2, 0.0,
+                                    B, N, G, LDF, dh, 1, _ffi.ptr(ws), self._xf, st), "sa_favor_scan_b_cum(dk')")
+        # dv runs on the states the dk' scan just built (same a = q', b = d attn * inv, reversed)
+        _ck(lib.sa_favor_scan_a_state(_ffi.ptr(qf), _ffi.ptr(kf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dv), qs, 0, None, B, N, G, LDF, dh, 1, 0,
+                                      _ffi.ptr(ws), 3 | self._xf, st), "sa_favor_scan_a_state(dv)")
+        pop = self._proj_op()
+        tsum = torch.empty(R * G, dtype=f32, device=dev)
+        if self._xf:   # fp32 parity mode: feature-map backward, then the exact-fp32 dgrad GEMM with the -|x|^2 part as addend
+            dddq, dddk = torch.empty_like(qf), torch.empty_like(kf)
+            dqg = torch.empty(R, G * dh, dtype=f32, device=dev)
+            dkg = torch.empty(R, G * dh, dtype=f32, device=dev)
+            _ck(lib.sa_favor_features_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), G * dh, 0, G, dh, 1, _ffi.ptr(dddq), _ffi.ptr(dqg),
+                                          None, None, R * G, m, LDF, st), "favor_features_bwd(q)")
+            _ck(lib.sa_favor_features_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), G * dh, 0, G, dh, 0, _ffi.ptr(dddk), _ffi.ptr(dkg),
+                                          _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, st), "favor_features_bwd(k)")
+            rg = (1, 1, R * G)
+            dqg = pop.dgrad(dddq.view(1, 1, 1, R * G, LDF), rg, addend=dqg.view(1, 1, 1, R * G, dh), fwd_out_stride=LDF).view(R, G * dh)
+            dkg = pop.dgrad(dddk.view(1, 1, 1, R * G, LDF), rg, addend=dkg.view(1, 1, 1, R * G, dh), fwd_out_stride=LDF).view(R, G * dh)
+            dq[:, : G * dh] = dqg
+            dk[:, : G * dh] = dkg
+        else:          # throughput mode: one launch per side straight into the global-head columns of dq / dk (d loss / d dd never exists)
+            ps = self._pop[2]
+            _ck(lib.sa_favor_features_project_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), qs, G, _ffi.ptr(ps), 1, _ffi.ptr(dq),
+                                                  None, None, R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(q)")
+            _ck(lib.sa_favor_features_project_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), qs, G, _ffi.ptr(ps), 0, _ffi.ptr(dk),
+                                                  _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(k)")
+
     def bwd(self, dx2, sv, B, N, gc: _GradCtx):
         self._sync()
         lib, st, dev, T = _ffi.lib(), _ffi.stream(), dx2.device, self.dtype
-        R, H, G, L, dh, m, LDF = B * N, self.H, self.G, self.L, self.dh, self.m, self.LDF
+        R, H, G, L, dh = B * N, self.H, self.G, self.L, self.dh
         inner = H * dh
         f32 = torch.float32
         ops, sa, ff = self.ops, self.sa, self.ff
@@ -918,133 +1004,45 @@ class _LayerEngine:
         gc.wgrad(ops["to_out"], _as5(sv["attnT"]), _as5(dFa), gc.buf(sa.to_out.weight), gc.buf(sa.to_out.bias))
         gc.done(sa.to_out.weight, sa.to_out.bias)
         dattn = ops["to_out"].dgrad(_as5(dFa), r5, out_dtype=f32).view(R, inner)
-        q, k, v, attn = sv["q"], sv["k"], sv["v"], sv["attn"]
+        q, v, attn = sv["q"], sv["v"], sv["attn"]
         fused_qkv = "to_qkv" in ops and q.stride(0) == 3 * inner
         dqkv_lp = None
-        local_done = False
         if fused_qkv:   # gradients as column blocks of one matrix, like q / k / v themselves: one cast, one wgrad, one dgrad below
             dqkv = torch.empty(R, 3 * inner, dtype=f32, device=dev)
             dq, dk, dv = dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:]
-            if T == torch.bfloat16 and (G == 0 or sv.get("fused")) and not debug.host("no_lp_mirrors"):
+            if T == torch.bfloat16 and (G == 0 or sv.get("fused")):
                 dqkv_lp = torch.empty(R, 3 * inner, dtype=T, device=dev)   # bf16 mirror written by the same kernels: operand of the q|k|v weight / data gradient
                 dq_lp, dk_lp, dv_lp = dqkv_lp[:, :inner], dqkv_lp[:, inner:2 * inner], dqkv_lp[:, 2 * inner:]
         else:
-            dq = torch.empty(R, inner, dtype=f32, device=dev)
-            dk = torch.empty(R, inner, dtype=f32, device=dev)
-            dv = torch.empty(R, inner, dtype=f32, device=dev)
+            dq, dk, dv = (torch.empty(R, inner, dtype=f32, device=dev) for _ in range(3))
         if not fused_qkv or dqkv_lp is None or (self.layer_pos is not None and G > 0):    # (rotated global heads: dq / dk are rotated back below, then cast)
             dqkv_lp = dq_lp = dk_lp = dv_lp = None
         qs = dq.stride(0)   # == q.stride(0): the kernels below address v / dv (and dq / dk) with one row stride
         assert qs == q.stride(0) == v.stride(0)
+        dqkr = None          # dq | dk of the local heads in rotated space, when they rode in the FAVOR+ launches
         if G > 0 and sv.get("fused"):
-            tiles, ps = self._proj_tiles()
-            nst = lib.sa_favor_fused_state_bytes(B, N, G, m) // 4
-            if self._ws is None or self._ws.numel() < nst or self._ws.device != dev:
-                self._ws = torch.empty(nst, dtype=f32, device=dev)
-            dden = torch.empty(R * G, dtype=f32, device=dev)
-            tsum = torch.empty(B * G * ((N + 63) // 64), dtype=f32, device=dev)
-            la_args = None
-            if L > 0 and sv.get("scan_state") is not None and not debug.host("no_attn_colaunch") and not pa:
-                # the local-window heads' backward blocks ride in the FAVOR+ launches (as in the forward pass); dq / dk of the local heads come out in ROTATED
-                # space (dqkr) and are rotated back below
-                dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
-                Db = torch.empty(R * L, dtype=f32, device=dev)
-                la_args = _ffi.LocalAttnArgs()
-                la_args.q, la_args.k, la_args.v = sv["qr"].data_ptr(), sv["kr"].data_ptr(), v.data_ptr()
-                (la_args.q_stride, la_args.q_off, la_args.k_stride, la_args.k_off, la_args.v_stride, la_args.v_off, la_args.o_stride,
-                 la_args.o_off) = L * dh, 0, L * dh, 0, qs, G * dh, inner, G * dh
-                la_args.out, la_args.dout, la_args.lse_in = attn.data_ptr(), dattn.data_ptr(), sv["lse"].data_ptr()
-                la_args.dq, la_args.dk, la_args.dv, la_args.Dbuf = dqkr[0].data_ptr(), dqkr[1].data_ptr(), dv.data_ptr(), Db.data_ptr()
-                la_args.dv_lp = dv_lp.data_ptr() if dv_lp is not None else None
-                la_args.L, la_args.W = L, self.W
-
-            def favor_bwd(la):
-                return lib.sa_favor_fused_bwd(_ffi.ptr(q), _ffi.ptr(k), _ffi.ptr(v), qs, _ffi.ptr(tiles), _ffi.ptr(ps), _ffi.ptr(sv["offq"]), _ffi.ptr(sv["amq"]),
-                                              _ffi.ptr(sv["offk"]), _ffi.ptr(sv["gws"]), _ffi.ptr(dattn), _ffi.ptr(attn), inner, _ffi.ptr(sv["inv"]), _ffi.ptr(dq),
-                                              _ffi.ptr(dk), _ffi.ptr(dv), B, N, G, m, _ffi.ptr(sv.get("scan_state")), _ffi.ptr(self._ws), _ffi.ptr(dden), _ffi.ptr(tsum),
-                                              _ffi.ptr(dq_lp), _ffi.ptr(dk_lp), _ffi.ptr(dv_lp), ctypes.byref(la) if la is not None else None, st)
-            t0 = _favor_bracket_begin()
-            rc = favor_bwd(la_args)
-            if rc == _ffi.SA_EUNSUPPORTED and la_args is not None:   # exact-fp32 local attention / unpaired launches: separate launches below
-                la_args = None
-                rc = favor_bwd(None)
-            _ck(rc, "sa_favor_fused_bwd")
-            _favor_bracket_end(t0, "favor_fdden+fpair_states_b+fpair_b_a+fkey_fix" + ("_la" if la_args is not None else ""),
-                               2.0 * B * N * G * FAVOR_FWD_FLOP_PER_HEAD_ROW(m, dh))
-            local_done = la_args is not None
-            sv["scan_state"] = None
+            dqkr = self._favor_fused_bwd(sv, dattn, dq, dk, dv, dq_lp, dk_lp, dv_lp, B, N, pa)
         elif G > 0:
-            qf, kf, Z, inv = sv["qf"], sv["kf"], sv["Z"], sv["inv"]
-            dden = torch.empty(R * G, dtype=f32, device=dev)
-            _ck(lib.sa_favor_dden(_ffi.ptr(dattn), _ffi.ptr(attn), inner, 0, G, dh, _ffi.ptr(inv), _ffi.ptr(dden), R * G, st), "sa_favor_dden")
-            ws = self._scan_ws(B, N, G, dev)
-            dqf = torch.empty_like(qf)
-            dkf = torch.empty_like(kf)
-            shared_dv = False
-            if Z is None:   # forward ran the fused form: the cumulative terms are rebuilt inside the scans as well
-                kept = sv.get("scan_state")   # the forward's chunk states: same (a = k', b = v) -> no state / prefix passes for dq'
-                _ck(lib.sa_favor_scan_b_cum(_ffi.ptr(kf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dqf), _ffi.ptr(dden), 1, 1e-6,
-                                            B, N, G, LDF, dh, 0, _ffi.ptr(kept if kept is not None else ws), (1 if kept is not None else 0) | self._xf, st),
-                    "sa_favor_scan_b_cum(dq')")
-                sv["scan_state"] = None
-                _ck(lib.sa_favor_scan_b_cum(_ffi.ptr(qf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dkf), _ffi.ptr(dden), 2, 0.0,
-                                            B, N, G, LDF, dh, 1, _ffi.ptr(ws), self._xf, st), "sa_favor_scan_b_cum(dk')")
-                shared_dv = True
-            else:
-                _ck(lib.sa_favor_scan_b(_ffi.ptr(kf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dqf), _ffi.ptr(dden), _ffi.ptr(Z),
-                                        1e-6, B, N, G, LDF, dh, 0, _ffi.ptr(ws), st), "sa_favor_scan_b(dq')")
-                rr = torch.empty_like(qf)
-                _ck(lib.sa_cumsum_rows(_ffi.ptr(qf), _ffi.ptr(dden), _ffi.ptr(rr), B, N, G, LDF, 1, _ffi.ptr(ws), st), "sa_cumsum_rows(rev)")
-                _ck(lib.sa_favor_scan_b(_ffi.ptr(qf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dkf), None, _ffi.ptr(rr), 0.0,
-                                        B, N, G, LDF, dh, 1, _ffi.ptr(ws), st), "sa_favor_scan_b(dk')")
-            if shared_dv:   # dv runs on the states the dk' scan just built (same a = q', b = d attn * inv, reversed)
-                _ck(lib.sa_favor_scan_a_state(_ffi.ptr(qf), _ffi.ptr(kf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dv), qs, 0, None, B, N, G, LDF, dh, 1, 0,
-                                              _ffi.ptr(ws), 3 | self._xf, st), "sa_favor_scan_a_state(dv)")
-            else:
-                _ck(lib.sa_favor_scan_a(_ffi.ptr(qf), _ffi.ptr(kf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dv), qs, 0, None, B, N, G, LDF, dh, 1, 0,
-                                        _ffi.ptr(ws), st), "sa_favor_scan_a(dv)")
-            pop = self._proj_op()
-            tsum = torch.empty(R * G, dtype=f32, device=dev)
-            if self._xf:   # fp32 parity mode: feature-map backward, then the exact-fp32 dgrad GEMM with the -|x|^2 part as addend
-                dddq, dddk = torch.empty_like(qf), torch.empty_like(kf)
-                dqg = torch.empty(R, G * dh, dtype=f32, device=dev)
-                dkg = torch.empty(R, G * dh, dtype=f32, device=dev)
-                _ck(lib.sa_favor_features_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), G * dh, 0, G, dh, 1, _ffi.ptr(dddq), _ffi.ptr(dqg),
-                                              None, None, R * G, m, LDF, st), "favor_features_bwd(q)")
-                _ck(lib.sa_favor_features_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), G * dh, 0, G, dh, 0, _ffi.ptr(dddk), _ffi.ptr(dkg),
-                                              _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, st), "favor_features_bwd(k)")
-                rg = (1, 1, R * G)
-                dqg = pop.dgrad(dddq.view(1, 1, 1, R * G, LDF), rg, addend=dqg.view(1, 1, 1, R * G, dh), fwd_out_stride=LDF).view(R, G * dh)
-                dkg = pop.dgrad(dddk.view(1, 1, 1, R * G, LDF), rg, addend=dkg.view(1, 1, 1, R * G, dh), fwd_out_stride=LDF).view(R, G * dh)
-                dq[:, : G * dh] = dqg
-                dk[:, : G * dh] = dkg
-            else:          # throughput mode: one launch per side straight into the global-head columns of dq / dk (d loss / d dd never exists)
-                ps = self._pop[2]
-                _ck(lib.sa_favor_features_project_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), qs, G, _ffi.ptr(ps), 1, _ffi.ptr(dq),
-                                                      None, None, R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(q)")
-                _ck(lib.sa_favor_features_project_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), qs, G, _ffi.ptr(ps), 0, _ffi.ptr(dk),
-                                                      _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(k)")
+            self._favor_chunked_bwd(sv, dattn, dq, dk, dv, B, N)
         if L > 0:
             cosb, sinb = self._rot_tables(N, dev)
-            if not local_done and pa:
+            if dqkr is None:      # separate launch (chunked route, attn_dropout, exact-fp32 local attention)
                 dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
                 Db = torch.empty(R * L, dtype=f32, device=dev)
-                _ck(lib.sa_local_attn_bwd_dropout(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
-                                                  inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W,
-                                                  dh, _ffi.ptr(dv_lp), pa, seed, self.site + 2, st), "sa_local_attn_bwd_dropout")
-            elif not local_done:
-                dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
-                Db = torch.empty(R * L, dtype=f32, device=dev)
-                _ck(lib.sa_local_attn_bwd(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
-                                          inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W, dh,
-                                          _ffi.ptr(dv_lp), st), "sa_local_attn_bwd")
-            dqr, dkr = dqkr[0], dqkr[1]
+                if pa:
+                    _ck(lib.sa_local_attn_bwd_dropout(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
+                                                      inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W,
+                                                      dh, _ffi.ptr(dv_lp), pa, seed, self.site + 2, st), "sa_local_attn_bwd_dropout")
+                else:
+                    _ck(lib.sa_local_attn_bwd(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
+                                              inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W, dh,
+                                              _ffi.ptr(dv_lp), st), "sa_local_attn_bwd")
             if fused_qkv:   # dq | dk are column blocks of one matrix: one launch
                 _ck(lib.sa_rotary_groups(_ffi.ptr(dqkr), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, 2, R * L * dh, inner, _ffi.ptr(dq_lp), st),
                     "sa_rotary_groups^T(q|k)")
             else:
-                _ck(lib.sa_rotary(_ffi.ptr(dqr), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(q)")
-                _ck(lib.sa_rotary(_ffi.ptr(dkr), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dk), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(k)")
+                _ck(lib.sa_rotary(_ffi.ptr(dqkr[0]), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(q)")
+                _ck(lib.sa_rotary(_ffi.ptr(dqkr[1]), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dk), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(k)")
         self._rotate_global(dq, dk, B, N, 1)
         xaT = _as5(sv["xaT"])
         base = _as5(dx1) if self.rezero else None

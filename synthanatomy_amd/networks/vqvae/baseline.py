@@ -301,8 +301,8 @@ class _Conv1Stage:
         """x: the raw fp32 volume [N, D, H, W]."""
         N, D, H, W = x.shape
         Do, Ho, Wo, cout = D // 2, H // 2, W // 2, self.op.cout
-        fused = (self.dtype == torch.bfloat16 and cout == 128 and not debug.host("no_conv1_fused") and not debug.deterministic())   # (its weight gradient ends in fp32 atomics)
-        if (D % 2 or H % 2 or W % 2 or Wo < 2 or N * Do * Ho * Wo < self.GEMM_MIN_CELLS or debug.host("no_conv1_gemm")   # generic stage
+        fused = (self.dtype == torch.bfloat16 and cout == 128 and not debug.deterministic())   # (its weight gradient ends in fp32 atomics)
+        if (D % 2 or H % 2 or W % 2 or Wo < 2 or N * Do * Ho * Wo < self.GEMM_MIN_CELLS   # generic stage
                 or (self.mixed and not fused)):      # (an f16 forward chain has the fused kernel and the generic stage, not the im2col route)
             vec = vec_of(self.dtype)
             xc = cast_pad(x.unsqueeze(-1), self.op.fwd_dtype, vec)
@@ -377,7 +377,7 @@ class _ConvT1Stage:
         self.taps_fwd.weight = self.taps_bwd.weight = self.mod.weight
 
     def _gemm(self, x):
-        return (x.numel() // 128 >= self.GEMM_MIN_CELLS and not debug.host("convt1_direct")) or debug.deterministic()   # (the direct kernels accumulate with atomics)
+        return x.numel() // 128 >= self.GEMM_MIN_CELLS or debug.deterministic()   # (the direct kernels accumulate with atomics)
 
     def fwd(self, x, tape):
         N, D, H, W, C = x.shape

@@ -392,8 +392,8 @@ def test_layernorm_kernels(R, C):
     assert _rel(dx, xr.grad) < 1e-5 and _rel(dw, wr.grad) < 1e-4 and _rel(db, br.grad) < 1e-4
 
 
-@pytest.mark.parametrize("N,segmented", [(37, False), (37, True), (300, True), (1400, True)])
-def test_causal_scan_kernels_against_quadratic_form(N, segmented):
+@pytest.mark.parametrize("N", [37, 300, 1400])
+def test_causal_scan_kernels_against_quadratic_form(N):
     from synthanatomy_amd import _ffi
     lib, st = _ffi.lib(), _ffi.stream()
     torch.manual_seed(2)
@@ -405,14 +405,11 @@ def test_causal_scan_kernels_against_quadratic_form(N, segmented):
     v = torch.randn(B * N, 2 * G * dv)  # global heads in the first G*dv columns of a wider row
     ref = P.causal_linear_attention(qf[..., :m].permute(0, 2, 1, 3), kf[..., :m].permute(0, 2, 1, 3), v[:, :G * dv].view(B, N, G, dv).permute(0, 2, 1, 3))
     qd, kd, vd = qf.cuda(), kf.cuda(), v.cuda()
-    Z = torch.empty_like(kd)
     inv = torch.empty(B * N * G, device="cuda")
     out = torch.zeros(B * N, 2 * G * dv, device="cuda")
-    ws = torch.empty(lib.sa_favor_scan_workspace_bytes(B, N, G, LDF, dv) // 4, device="cuda") if segmented else None
-    _ffi.check(lib.sa_cumsum_rows(_ffi.ptr(kd), None, _ffi.ptr(Z), B, N, G, LDF, 0, _ffi.ptr(ws), st))
-    _ffi.check(lib.sa_favor_den(_ffi.ptr(qd), _ffi.ptr(Z), 1e-6, _ffi.ptr(inv), B * N * G, m, LDF, st))
-    _ffi.check(lib.sa_favor_scan_a(_ffi.ptr(kd), _ffi.ptr(qd), _ffi.ptr(vd), 2 * G * dv, 0, None, _ffi.ptr(out), 2 * G * dv, 0, _ffi.ptr(inv), B, N, G, LDF, dv, 0, 0,
-                                   _ffi.ptr(ws), st))
+    ws = torch.empty(lib.sa_favor_scan_workspace_bytes(B, N, G, LDF, dv) // 4, device="cuda")
+    _ffi.check(lib.sa_favor_scan_a_norm(_ffi.ptr(kd), _ffi.ptr(qd), _ffi.ptr(vd), 2 * G * dv, 0, _ffi.ptr(out), 2 * G * dv, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dv,
+                                        _ffi.ptr(ws), 0, st))
     got = out[:, :G * dv].view(B, N, G, dv).permute(0, 2, 1, 3)
     assert _rel(got, ref) < 1e-4
     assert float(out[:, G * dv:].abs().max()) == 0.0  # only the addressed head block is written
@@ -420,7 +417,7 @@ def test_causal_scan_kernels_against_quadratic_form(N, segmented):
 
 @pytest.mark.parametrize("N,reverse", [(37, 0), (37, 1), (200, 1), (1400, 0)])
 def test_causal_scan_variants_against_einsum(N, reverse):
-    """Every mode the backward uses: reversed order, per-position scales, accumulate, scan B with its extra term; VALU path == MFMA path."""
+    """Every mode the backward uses: reversed order, per-position scales, accumulate, scan B with both cumulative extra terms, the fused normaliser."""
     from synthanatomy_amd import _ffi
     lib, st = _ffi.lib(), _ffi.stream()
     torch.manual_seed(5)
@@ -433,32 +430,16 @@ def test_causal_scan_variants_against_einsum(N, reverse):
     cc = torch.randn(B, N, G, dv, dtype=torch.float64)
     bs = torch.rand(B, N, G, dtype=torch.float64) + 0.5
     ys = torch.rand(B, N, G, dtype=torch.float64) + 0.5
-    ev = torch.zeros(B, N, G, LDF, dtype=torch.float64)
-    ev[..., :m] = torch.randn(B, N, G, m)
     y0 = torch.randn(B, N, G, dv, dtype=torch.float64)
     tri = torch.tril(torch.ones(N, N, dtype=torch.float64))
     if reverse:
         tri = tri.t()                                  # j >= i
     bsc = bb * bs[..., None]
     refA = torch.einsum("bigm,bjgm,ij,bjgd->bigd", c, a, tri, bsc) * ys[..., None] + y0
-    refB = torch.einsum("bjgm,bjgd,ij,bigd->bigm", a, bsc, tri, cc * ys[..., None]) + bs[..., None] * (ev + 0.25)
-    refB[..., m:] = refB[..., m:]                      # padding columns carry only the extra term
     f = lambda t: t.float().cuda().contiguous()
-    ad, cd, bd, ccd, bsd, ysd, evd = f(a), f(c), f(bb.reshape(B * N, G * dv)), f(cc.reshape(B * N, G * dv)), f(bs), f(ys), f(ev)
+    ad, cd, bd, ccd, bsd, ysd = f(a), f(c), f(bb.reshape(B * N, G * dv)), f(cc.reshape(B * N, G * dv)), f(bs), f(ys)
     ws = torch.empty(lib.sa_favor_scan_workspace_bytes(B, N, G, LDF, dv) // 4, device="cuda")
-    outs = []
-    for w in (ws, None):
-        ya = f(y0.reshape(B * N, G * dv))
-        _ffi.check(lib.sa_favor_scan_a(_ffi.ptr(ad), _ffi.ptr(cd), _ffi.ptr(bd), G * dv, 0, _ffi.ptr(bsd), _ffi.ptr(ya), G * dv, 0, _ffi.ptr(ysd), B, N, G, LDF, dv,
-                                       reverse, 1, _ffi.ptr(w), st))
-        yb = torch.zeros(B, N, G, LDF, device="cuda")
-        _ffi.check(lib.sa_favor_scan_b(_ffi.ptr(ad), _ffi.ptr(bd), G * dv, 0, _ffi.ptr(bsd), _ffi.ptr(ccd), G * dv, 0, _ffi.ptr(ysd), _ffi.ptr(yb), _ffi.ptr(bsd),
-                                       _ffi.ptr(evd), 0.25, B, N, G, LDF, dv, reverse, _ffi.ptr(w), st))
-        outs.append((ya, yb))
-        assert _rel(ya.view(B, N, G, dv).cpu().double(), refA) < 1e-4
-        assert _rel(yb[..., :m].cpu().double(), refB[..., :m]) < 1e-4
-    assert _rel(outs[0][0], outs[1][0]) < 1e-4 and _rel(outs[0][1][..., :m], outs[1][1][..., :m]) < 1e-4
-    # ---- the fused running sums (chunked MFMA path): cumulative extra terms and the normaliser without cumsum / den passes
+    # ---- the running sums ride in the scans: cumulative extra terms and the normaliser
     trif = tri
     cum_a = torch.einsum("ij,bjgm->bigm", trif, a)                                   # sum_{j <= i (scan order)} a_j
     cum_aw = torch.einsum("ij,bjgm->bigm", trif, a * bs[..., None])                  # ... weighted by ex_scale_j
