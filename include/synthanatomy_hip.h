@@ -233,6 +233,33 @@ int64_t sa_fourier_loss_workspace_bytes(int64_t B, int C, int D, int H, int W);
 int sa_ms_ssim(const float *x, const float *y, int B, int C, int D, int H, int W, const float *win, int win_size, int levels, const float *weights,
                float c1, float c2, float *out_b, float *level_means, void *ws, void *stream);
 int64_t sa_ms_ssim_workspace_bytes(int B, int C, int D, int H, int W, int win_size, int levels);
+/* Training augmentations of the VQ-VAE data path (reference src/utils/vqvae.py:183-371; run_vqvae.py --augmentation / --patch_size /
+ * --no_augmented_extractions).  x [B, 1, Di, Hi, Wi] -> y [B, 1, Do, Ho, Wo], fp32 contiguous device tensors, y != x; params: B records in device (or
+ * pinned host) memory.  Two launches on the stream, no host synchronisation.  Axis 0 = D, 1 = H, 2 = W; o = an output voxel, n_out = (Do, Ho, Wo).
+ *   SA_AUG_IDENTITY     y[o] = x[off + o]                                                   (off + n_out <= the input's dims)
+ *   SA_AUG_SIGNED_PERM  source axis perm[a] takes off[perm[a]] + (sign[a] > 0 ? o_a : n_out[a] - 1 - o_a): a crop at off followed by any composition of
+ *                       np.flip / np.rot90, bit-exact                                       (perm a permutation, the crop inside the input)
+ *   SA_AUG_AFFINE       trilinear sample at p = M . [o - (n_out - 1) / 2; 1] + (ext - 1) / 2 inside the source window [off, off + ext) (M row-major 3 x 4;
+ *                       the centred voxel grid with align_corners = True); a corner outside the window counts as 0
+ * then, each behind its bit of `flags` and in this order: gamma ((v - min) / (max - min + 1e-7))^gamma (max - min) + min with the sample's min / max after
+ * the spatial stage; + shift; + noise_std * n; clamp to [0, 1].  n: Box-Muller on Philox4x32-10 words, a pure function of (seed, sample index b, voxel
+ * index inside the sample's output) -- exact indexing in csrc/augment.hip.  A record that breaks a condition above gives zeros for its sample and
+ * status 1.  ws: sa_augment_workspace_bytes(B) bytes (32 per sample), 8-byte aligned, ZERO before its first use and then left alone between calls (one
+ * call at a time per workspace); per sample four 64-bit words: [0], [1] the reduction words, [2] = the float min (low half) and max (high half) a gamma
+ * step used, [3] = status.  SA_EINVAL for null operands, y == x, B outside 1..65535 or a dim < 1; SA_EUNSUPPORTED for Do Ho Wo >= 2^31 - 16. */
+enum { SA_AUG_IDENTITY = 0, SA_AUG_AFFINE = 1, SA_AUG_SIGNED_PERM = 2 };
+enum { SA_AUG_GAMMA = 1, SA_AUG_SHIFT = 2, SA_AUG_NOISE = 4, SA_AUG_CLAMP = 8 };
+typedef struct sa_augment_params {
+    int32_t mode, flags;
+    int32_t off[3], ext[3];
+    int32_t perm[3], sign[3];
+    float M[12];
+    float gamma, shift, noise_std;
+    int32_t reserved[3];
+} sa_augment_params; /* 128 bytes */
+int sa_augment(const float *x, float *y, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, const sa_augment_params *params, uint64_t seed, void *ws,
+               void *stream);
+int64_t sa_augment_workspace_bytes(int B);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -12,6 +12,14 @@ by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_
 (network, optimizer, lr_scheduler, trainer, d_*) restored on resume, uint16 ``.npy`` code files.
 Inputs: ``.npy`` volumes (any of dir / glob / csv listing) or ``synthetic:<n>`` (uniform [0,1) volumes of ``--roi`` size).
 Multi-GPU: launch with torchrun; one process per GPU, RCCL.
+
+``--augmentation=True`` (MI355X-only switch, default False) turns on the reference's training augmentations (src/utils/vqvae.py:183-371, which upstream
+always applies in ``--mode=training``): every transform fires with ``--augmentation_probability``, ranges scale with ``--augmentation_strength``; without
+``--patch_size`` a random affine resample, with it a random crop, three flips and three 90-degree rotations; then gamma contrast, intensity shift,
+Gaussian noise and the clamp to [0, 1].  Training batches AND the evaluator's batches go through it (as upstream's evaluation transform does), on the
+device in two launches of ``sa_augment``; the draws are keyed on (seed, epoch, subject), the noise on (seed, iteration).  With the default
+False the loop is untouched and ``--augmentation_probability`` stays inert.  ``--patch_size`` crops training batches with or without the switch, and
+``--mode=extracting --no_augmented_extractions=n`` writes n augmented extractions ``<name>_<i>`` per subject (no switch needed, as upstream).
 """
 import os
 import sys
@@ -31,7 +39,7 @@ DEFAULTS = dict(
     discriminator_network="baseline_discriminator", discriminator_learning_rate=0.0005, discriminator_loss="least_square",
     generator_loss="least_square", use_adversarial_adaptive_weight=False, adaptive_adversarial_weight_threshold=0,
     adaptive_adversarial_weight_value=1, initial_factor_value=0, initial_factor_steps=25, max_factor_steps=50, max_factor_value=5, normalize=True,
-    roi=((16, 176), (16, 240), (96, 256)), batch_size=3, patch_size=None, eval_batch_size=3, eval_patch_size=None, training_epoch_length=None,
+    roi=((16, 176), (16, 240), (96, 256)), augmentation=False, batch_size=3, patch_size=None, eval_batch_size=3, eval_patch_size=None, training_epoch_length=None,
     num_workers=8, prefetch_factor=8, starting_epoch=0, network="baseline_vqvae", use_subpixel_conv=False, use_slim_residual=True, no_levels=3,
     downsample_parameters=((4, 2, 1, 1),) * 3, upsample_parameters=((4, 2, 1, 0, 1),) * 3, no_res_layers=3, no_channels=256, codebook_type="ema",
     num_embeddings=(256,), embedding_dim=(256,), embedding_init=("normal",), commitment_cost=(0.25,), decay=(0.99,), decay_warmup=None,
@@ -47,12 +55,16 @@ def _load_volume(path, cfg, gen, dev):
     if path.startswith("synthetic"):   # a volume that depends on its NAME only (not on how many were drawn before it): resumable, rank-independent
         g = torch.Generator(device=dev).manual_seed(cfg["seed"] * 1000003 + int(path.split("_")[-1]))
         return torch.rand(1, *_roi_shape(cfg), generator=g, device=dev)
+    return _read_volume(path, cfg).to(dev)
+
+
+def _read_volume(path, cfg):
     v = torch.from_numpy(np.load(path).astype(np.float32))
     if v.dim() == 3:
         v = v[None]
     if cfg["normalize"]:
         v = (v - v.min()) / (v.max() - v.min() + 1e-8)  # ScaleIntensityd(0, 1)
-    return v.to(dev)
+    return v
 
 
 def _batches(files, order, bs, cfg, gen, dev):
@@ -62,6 +74,52 @@ def _batches(files, order, bs, cfg, gen, dev):
         yield chunk, torch.stack([_load_volume(f, cfg, gen, dev) for f in chunk])
 
 
+def _noise_seed(seed, counter, stream=0):
+    """64-bit noise seed of one batch: a splitmix64 hash of (--seed, stream, counter); stream 0 = training iterations, 1 = evaluator, 2 = extraction.
+    The callers fold the rank into the counter (counter * world + rank)."""
+    z = (int(seed) * 0x9E3779B97F4A7C15 + int(counter) * 0xBF58476D1CE4E5B9 + int(stream) * 0x94D049BB133111EB + 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
+def _load_input(path, cfg, dev):
+    """A volume for the sa_augment path and where the ROI starts inside it: the kernel crops (CenterSpatialCropd for three ints, SpatialCropd for three
+    pairs); a file smaller than the ROI is cropped and mirror-padded on the host first (SpatialPadd SYMMETRIC, the rare path)."""
+    from synthanatomy_amd.utils.vqvae import pad_to_roi, roi_shape, roi_window
+    if path.startswith("synthetic") or not cfg["roi"]:
+        return _load_volume(path, cfg, None, dev), [0, 0, 0]
+    v = _read_volume(path, cfg)
+    start, size = roi_window(cfg["roi"], v.shape[-3:])
+    if size != roi_shape(cfg["roi"]):
+        crop = v[..., start[0]:start[0] + size[0], start[1]:start[1] + size[1], start[2]:start[2] + size[2]]
+        v, start = torch.from_numpy(np.ascontiguousarray(pad_to_roi(crop.numpy(), cfg["roi"]))), [0, 0, 0]
+    return v.to(dev), start
+
+
+def _augmented_batches(items, bs, cfg, dev, mode, noise_seed):
+    """Batches through sa_augment.  ``items``: (output name, file, epoch key, subject index) -- the draws of a sample depend on (--seed, epoch key, subject
+    index) only (synthanatomy_amd.utils.vqvae.draw_augmentation); ``noise_seed(k)`` is the noise seed of batch k.  Yields (names, batch, noise seed)."""
+    from synthanatomy_amd.utils.vqvae import draw_augmentation, hip_augment, in_window, roi_shape
+    for i in range(0, len(items), bs):
+        chunk, vols, recs = items[i:i + bs], [], []
+        for _, f, epoch_key, subject in chunk:
+            v, start = _load_input(f, cfg, dev)
+            dims = roi_shape(cfg["roi"]) if cfg["roi"] else list(v.shape[-3:])
+            recs.append(in_window(draw_augmentation(cfg, mode, cfg["seed"], epoch_key, subject, dims), start))
+            vols.append(v)
+        ns = noise_seed(i // bs)
+        yield [c[0] for c in chunk], hip_augment(torch.stack(vols), np.stack(recs), cfg["patch_size"] or dims, ns), ns
+
+
+def _augmented_name(f, i):
+    """get_subjects' augmentation_id in the file name (reference src/utils/vqvae.py:601-608): <name>_<i><extension>"""
+    for ext in (".nii.gz", ".nii", ".npy"):
+        if f.endswith(ext):
+            return f[:-len(ext)] + f"_{i}" + ext
+    return f"{f}_{i}"
+
+
 def build_network(cfg, dev):
     from synthanatomy_amd.networks.vqvae.configure import get_vqvae_network
     cfg = dict(cfg)
@@ -69,10 +127,12 @@ def build_network(cfg, dev):
     return get_vqvae_network(cfg).to(dev)
 
 
-def _evaluate(net, files, cfg, gen, dev, rank, world, win_size):
+def _evaluate(net, files, cfg, gen, dev, rank, world, win_size, epoch=0, index_base=0):
     """The evaluator of run_vqvae.py:122-146,248-289 over the validation subjects: ``mse`` is the mean reconstruction MSE this build has always
     logged (``hip_mse``), ``metrics`` the reference's Metric-MS-SSIM_<w> (when ``win_size`` is not None), Metric-MAE and Metric-MSE-Reconstruction
-    (synthanatomy_amd.metrics.vqvae; each all-reduces its sum and count over the ranks in ``compute``)."""
+    (synthanatomy_amd.metrics.vqvae; each all-reduces its sum and count over the ranks in ``compute``).  With ``--augmentation=True`` the batches are
+    augmented like the training ones (upstream builds the evaluation transform with the same patch_size and augmentations), drawn for
+    (``epoch``, ``index_base`` + the subject's index)."""
     from synthanatomy_amd.losses.vqvae import hip_mse
     from synthanatomy_amd.metrics.vqvae import MAE, MSE, MultiScaleSSIM
     import torch.distributed as dist
@@ -86,7 +146,12 @@ def _evaluate(net, files, cfg, gen, dev, rank, world, win_size):
     tot = torch.zeros(2, device=dev, dtype=torch.float64)
     with torch.no_grad():
         order = shard_for_rank(len(files), rank, world, shuffle=False, pad=False)
-        for _, x in _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev):
+        if cfg.get("augmentation"):
+            batches = _augmented_batches([(files[k], files[k], epoch, index_base + k) for k in order], cfg["eval_batch_size"], cfg, dev, "training",
+                                         lambda k: _noise_seed(cfg["seed"], ((epoch << 24) + k) * world + rank, 1))
+        else:
+            batches = _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev)
+        for _, x, *_ in batches:
             rec = net(x)["reconstruction"][0]
             tot[0] += hip_mse(rec, x).double() * x.shape[0]
             tot[1] += x.shape[0]
@@ -154,18 +219,26 @@ def training(cfg, rank, local, world, dev):
             loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, state.epoch))
     # key metric (run_vqvae.py:122): MS-SSIM with get_ms_ssim_window's window; where the reference refuses to start (smallest side < 48), -MSE
     from synthanatomy_amd.utils.vqvae import get_ms_ssim_window
-    try:
-        win_size = get_ms_ssim_window(cfg)
+    try:      # (--augmentation with --patch_size: the evaluator sees patches, so they size the window unless --eval_patch_size does)
+        win_size = get_ms_ssim_window(dict(cfg, eval_patch_size=cfg["eval_patch_size"] or cfg["patch_size"]) if cfg["augmentation"] else cfg)
     except ValueError as e:
         win_size = None
         log(rank, f"MS-SSIM key metric unavailable ({e}): the best checkpoint is chosen by -validation mse")
     key_name = f"Metric-MS-SSIM_{win_size}-Reconstruction" if win_size is not None else None
     gen = torch.Generator(device=dev).manual_seed(cfg["seed"] + rank)
+    from synthanatomy_amd.utils.vqvae import check_patch_size
+    check_patch_size(cfg, "training")
+    augmenting = bool(cfg["augmentation"] or cfg["patch_size"])      # training batches go through sa_augment (--patch_size alone: the random crop only)
     for epoch in range(state.epoch, cfg["epochs"]):
         # DistributedSampler semantics: one epoch-seeded permutation shared by all ranks, padded so every rank runs the same number of steps
         order = shard_for_rank(len(files), rank, world, epoch=epoch, seed=cfg["seed"])
         done = 0
-        for names, x in _batches(files, order, cfg["batch_size"], cfg, gen, dev):
+        if augmenting:
+            batches = _augmented_batches([(files[k], files[k], epoch, k) for k in order], cfg["batch_size"], cfg, dev, "training",
+                                         lambda k: _noise_seed(cfg["seed"], (state.iteration + 1) * world + rank))
+        else:
+            batches = _batches(files, order, cfg["batch_size"], cfg, gen, dev)
+        for names, x, *noise_seed in batches:
             if trainer is not None:
                 res = trainer.iteration(x, x, epoch + 1)      # ignite's state.epoch is 1 during the first epoch (trainer.py:176)
                 loss = res["loss"]
@@ -183,6 +256,8 @@ def training(cfg, rank, local, world, dev):
                 extra = f" g_loss {float(res['g_loss']):.6f} d_loss {float(res['d_loss']):.6f} adv_weight {float(res['adversarial_weight']):.4f}" if res else ""
                 if baur:
                     extra += f" gdl_factor {loss_fn.get_gdl_factor():.6g}"
+                if augmenting:
+                    extra += f" input {'x'.join(str(n) for n in x.shape[2:])} noise_seed {noise_seed[0]:#018x}"
                 log(rank, f"epoch {epoch} it {state.iteration} loss {loss.item():.6f}{extra} perplexity {net.get_perplexity()[0].item():.2f} lr {opt.lr:.3e}")
             if done == epoch_length:
                 break
@@ -190,7 +265,7 @@ def training(cfg, rank, local, world, dev):
         if baur:                                          # ParamSchedulerHandler(epoch_level=True) at EPOCH_COMPLETED, state.epoch = finished epochs
             loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, epoch + 1))
         if (epoch + 1) % cfg["eval_every"] == 0 and val_files:
-            mse, metrics = _evaluate(net, val_files, cfg, gen, dev, rank, world, win_size)
+            mse, metrics = _evaluate(net, val_files, cfg, gen, dev, rank, world, win_size, epoch=epoch, index_base=len(files))
             log(rank, f"epoch {epoch} validation mse {mse:.6f}")
             log(rank, f"epoch {epoch} validation " + " ".join(f"{k} {v:.6f}" for k, v in metrics.items()))
             if rank == 0:                                                       # evaluator's key-metric checkpoint, key_metric_n_saved=1
@@ -215,7 +290,13 @@ def inference(cfg, rank, local, world, dev):
     with torch.no_grad():
         if cfg["mode"] == "extracting":
             order = shard_for_rank(len(files), rank, world, shuffle=False, pad=False)   # even_divisible=False: no duplicates, no collectives
-            for names, x in _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev):
+            n_aug = int(cfg["no_augmented_extractions"] or 0)
+            if n_aug > 0:      # every subject n_aug times, augmentation_id i drawn as "epoch" i (reference src/utils/vqvae.py:126-181,194-196)
+                batches = _augmented_batches([(_augmented_name(files[k], i), files[k], i, k) for k in order for i in range(n_aug)], cfg["eval_batch_size"], cfg,
+                                             dev, "extracting", lambda k: _noise_seed(cfg["seed"], k * world + rank, 2))
+            else:
+                batches = _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev)
+            for names, x, *_ in batches:
                 idx = net.index_quantize(x)[0]
                 rec = net.decode_samples([idx])
                 for n, i_, r_ in zip(names, idx.cpu().numpy(), rec.float().cpu().numpy()):
