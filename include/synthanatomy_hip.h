@@ -269,7 +269,8 @@ int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, f
  * The dense projections (to_q/to_k/to_v/to_out, FeedForward w1/w2, final to_out) are 1-tap sa_conv_fprop / sa_conv_wgrad. */
 
 /* out[r,:] = sum_t table_t[idx_t[per_position_t ? r % N : r], :]  (idx < 0 skips) -- token + spatial + positional embeddings
- * (performer.py:241-266); sa_embed_scatter is its gradient wrt one table (fp32 atomics). */
+ * (performer.py:241-266); sa_embed_scatter is its gradient wrt one table (fp32 atomics).  1 <= ntab <= 12 (also for sa_embed_step): token, three
+ * spatial, two axial positional and up to six conditioning tables, whose per-row index rows are -1 outside the conditioning's position. */
 int sa_embed_sum(int ntab, const float *const *tables, const int64_t *const *idx, const int32_t *per_position, int dim, int N,
                  int64_t R, float *out, void *stream);
 int sa_embed_scatter(const float *dy, float *dtable, const int64_t *idx, int per_position, int dim, int N, int64_t R, void *stream);

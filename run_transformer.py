@@ -7,6 +7,9 @@
 Training: codes -> ordering -> BOS pad -> Performer -> cross entropy, Adam, per-iteration ExponentialLR.  Inference: sample
 ``prod(spatial_shape)`` tokens autoregressively, revert the ordering and write uint16 ``.npy`` code grids (postfix "sample")
 that ``run_vqvae.py --mode=decoding`` consumes.  ``--n_embed`` is accepted as an alias of ``--n_embd`` (README vs. code).
+
+Conditioning (reference run_transformer.py:81-95,160-215,340-373): ``--conditioning_path=<csv|tsv with a 'subject' column> --conditionings=(age,sex)
+--conditioning_type=bos_replacement|prepending`` trains on / samples for the subjects the file covers, each conditioned on its own row.
 """
 import os
 import sys
@@ -39,6 +42,24 @@ def _load_codes(path, cfg, gen):
     return torch.from_numpy(np.load(path).astype(np.int64))
 
 
+def _conditioned_subjects(files, cfg, rank, what):
+    """the subjects of ``files`` the conditioning file covers + their values (utils/transformer.load_conditionings); sets cfg["conditioning_num_tokens"] and
+    logs it as the reference does (src/utils/transformer.py:225-235).  Without --conditionings: ``files`` as they are."""
+    if not cfg["conditionings"]:
+        return files, None
+    from synthanatomy_amd.utils.transformer import load_conditionings
+    kept, values, num_tokens = load_conditionings(files, cfg["conditioning_path"], cfg["conditionings"])
+    if not kept:
+        raise ValueError(f"--conditioning_path={cfg['conditioning_path']!r} covers none of the {len(files)} {what} subjects")
+    if cfg.get("conditioning_num_tokens") is None:
+        log(rank, "The conditioning vocab size is modified as follows:")
+        for i, c in enumerate(cfg["conditionings"]):
+            log(rank, f"\tTo {num_tokens[:i + 1]} due to {c}.")
+    cfg["conditioning_num_tokens"] = num_tokens
+    log(rank, f"{what} subjects with conditioning {tuple(cfg['conditionings'])}: {len(kept)} of {len(files)}")
+    return kept, values
+
+
 def build(cfg, dims, dev):
     from synthanatomy_amd.networks.transformers.img2seq_ordering import Ordering
     from synthanatomy_amd.networks.transformers.performer import Performer
@@ -54,17 +75,19 @@ def build(cfg, dims, dev):
                     feature_redraw_interval=cfg["feature_redraw_interval"], generalized_attention=cfg["generalized_attention"],
                     emb_dropout=cfg["emb_dropout"], ff_dropout=cfg["ff_dropout"], attn_dropout=cfg["attn_dropout"], use_rezero=cfg["use_rezero"],
                     fixed_position_emb=cfg["position_emb"] == "fixed", spatial_position_emb=cfg["spatial_position_emb"], spatial_shape=tuple(dims),
-                    compute_dtype=torch.bfloat16 if cfg["compute_dtype"] == "bf16" else torch.float32)
+                    compute_dtype=torch.bfloat16 if cfg["compute_dtype"] == "bf16" else torch.float32,
+                    conditioning_type=cfg["conditioning_type"],
+                    **(dict(conditioning_num_tokens=tuple(cfg["conditioning_num_tokens"])) if cfg.get("conditionings") else {}))
     return net.to(dev), ordering
 
 
-def _validation_ce(net, ordering, files, cfg, gen, dev, rank, world):
+def _validation_ce(net, ordering, files, cfg, gen, dev, rank, world, cond_values=None):
     """Mean cross entropy over the validation subjects -- the key metric of run_transformer.py:136-143 (the best-checkpoint rule keeps the
     HIGHEST score, so the score is the negated loss)."""
     import torch.distributed as dist
 
     from synthanatomy_amd.losses.transformer import CELoss
-    from synthanatomy_amd.utils.transformer import prepare_batch
+    from synthanatomy_amd.utils.transformer import conditioning_batch, prepare_batch
     was = net.training
     net.eval()
     tot = torch.zeros(2, device=dev, dtype=torch.float64)
@@ -72,9 +95,11 @@ def _validation_ce(net, ordering, files, cfg, gen, dev, rank, world):
     with torch.no_grad():
         order = shard_for_rank(len(files), rank, world, shuffle=False, pad=False)
         for i in range(0, len(order), cfg["eval_batch_size"]):
-            q = torch.stack([_load_codes(files[k], cfg, gen) for k in order[i:i + cfg["eval_batch_size"]]])
-            (x_in, _), x_tgt = prepare_batch({"quantization": q}, ordering.get_sequence_ordering(), cfg["vocab_size"], device=dev)
-            tot[0] += loss_fn(net(x_in).transpose(1, 2), x_tgt).double() * q.shape[0]
+            picks = order[i:i + cfg["eval_batch_size"]]
+            q = torch.stack([_load_codes(files[k], cfg, gen) for k in picks])
+            batch = {"quantization": q, **conditioning_batch(cond_values, cfg["conditionings"], picks)}
+            (x_in, cond), x_tgt = prepare_batch(batch, ordering.get_sequence_ordering(), cfg["vocab_size"], cfg["conditionings"], device=dev)
+            tot[0] += loss_fn(net(x_in, conditionings=cond).transpose(1, 2), x_tgt).double() * q.shape[0]
             tot[1] += q.shape[0]
     if world > 1:
         dist.all_reduce(tot)
@@ -86,10 +111,12 @@ def training(cfg, rank, local, world, dev):
     from synthanatomy_amd.losses.transformer import CELoss
     from synthanatomy_amd.runtime.ddp import GradReducer
     from synthanatomy_amd.runtime.optim import ExponentialLR, FlatParams, FusedAdam, TrainerState
-    from synthanatomy_amd.utils.transformer import prepare_batch
+    from synthanatomy_amd.utils.transformer import conditioning_batch, prepare_batch
     gen = torch.Generator().manual_seed(cfg["seed"] + rank)
-    files = list_inputs(cfg["training_subjects"], postfix="quantization_0")
+    # the subjects without usable conditioning leave BEFORE sharding: every rank shards the same kept list
+    files, cond_values = _conditioned_subjects(list_inputs(cfg["training_subjects"], postfix="quantization_0"), cfg, rank, "training")
     val_files = list_inputs(cfg["validation_subjects"], postfix="quantization_0")
+    val_files, val_cond_values = _conditioned_subjects(val_files, cfg, rank, "validation") if val_files else (val_files, None)
     dims = tuple(_load_codes(files[0], cfg, gen).shape)  # the reference peeks one batch for the latent shape (run_transformer.py:54-56)
     net, ordering = build(cfg, dims, dev)
     net.train()
@@ -121,10 +148,12 @@ def training(cfg, rank, local, world, dev):
         order = shard_for_rank(len(files), rank, world, epoch=epoch, seed=cfg["seed"])   # DistributedSampler: shared permutation, padded
         done = 0
         for i in range(0, len(order), cfg["batch_size"]):
-            q = torch.stack([_load_codes(files[k], cfg, gen) for k in order[i:i + cfg["batch_size"]]])
-            (x_in, _), x_tgt = prepare_batch({"quantization": q}, ordering.get_sequence_ordering(), cfg["vocab_size"], device=dev)
+            picks = order[i:i + cfg["batch_size"]]
+            q = torch.stack([_load_codes(files[k], cfg, gen) for k in picks])
+            batch = {"quantization": q, **conditioning_batch(cond_values, cfg["conditionings"], picks)}
+            (x_in, cond), x_tgt = prepare_batch(batch, ordering.get_sequence_ordering(), cfg["vocab_size"], cfg["conditionings"], device=dev)
             flat.zero_grad()
-            logits = net(x_in)
+            logits = net(x_in, conditionings=cond)
             loss = loss_fn(logits.transpose(1, 2), x_tgt)
             loss.backward()
             opt.step(grad_scale=red.finish())
@@ -137,7 +166,7 @@ def training(cfg, rank, local, world, dev):
                 break
         state.iteration = (epoch + 1) * epoch_length
         if (epoch + 1) % cfg["eval_every"] == 0 and val_files:
-            ce = _validation_ce(net, ordering, val_files, cfg, gen, dev, rank, world)
+            ce = _validation_ce(net, ordering, val_files, cfg, gen, dev, rank, world, val_cond_values)
             log(rank, f"epoch {epoch} validation ce {ce:.5f}")
             if rank == 0:
                 save_checkpoint(cfg, epoch + 1, to_save, key_metric=-ce)
@@ -146,8 +175,10 @@ def training(cfg, rank, local, world, dev):
 
 
 def inference(cfg, rank, local, world, dev):
-    from synthanatomy_amd.utils.transformer import prepare_inference_batch
-    files = list_inputs(cfg["validation_subjects"], postfix="quantization_0")[rank::world]
+    from synthanatomy_amd.utils.transformer import conditioning_batch, prepare_inference_batch
+    # conditioning_num_tokens comes from the same file as in training, before the network is built and the checkpoint loaded; the kept subjects are sharded
+    files, cond_values = _conditioned_subjects(list_inputs(cfg["validation_subjects"], postfix="quantization_0"), cfg, rank, "validation")
+    mine = list(range(len(files)))[rank::world]
     gen = torch.Generator().manual_seed(cfg["seed"] + rank)
     dims = tuple(_load_codes(files[0], cfg, gen).shape)
     net, ordering = build(cfg, dims, dev)
@@ -155,14 +186,17 @@ def inference(cfg, rank, local, world, dev):
     if path:
         load_network_state(net, path)
     net.eval()
-    for i in range(0, len(files), cfg["eval_batch_size"]):
-        chunk = files[i:i + cfg["eval_batch_size"]]
-        q = torch.zeros(len(chunk), *dims, dtype=torch.long)
-        (prefix, _), _ = prepare_inference_batch({"quantization": q}, cfg["vocab_size"], device=dev)
-        out = net.sample(prefix, temperature=cfg["temperature"], sample=cfg["sample"], top_k=cfg["top_k"])
-        for f, o in zip(chunk, out.cpu().numpy()):
-            save_npy(o, cfg["outputs_directory"], f, "sample", np.uint16)
-    log(rank, f"inference done: {len(files)} samples -> {cfg['outputs_directory']}")
+    # prepended conditionings decode on the O(N) sampler too (Performer.sample keeps the reference loop as ITS default for them)
+    how = dict(stateful=True) if cfg["conditionings"] and cfg["conditioning_type"] == "prepending" else {}
+    for i in range(0, len(mine), cfg["eval_batch_size"]):
+        picks = mine[i:i + cfg["eval_batch_size"]]
+        q = torch.zeros(len(picks), *dims, dtype=torch.long)
+        batch = {"quantization": q, **conditioning_batch(cond_values, cfg["conditionings"], picks)}
+        (prefix, cond), _ = prepare_inference_batch(batch, cfg["vocab_size"], cfg["conditionings"], device=dev)
+        out = net.sample(prefix, conditioning=cond, temperature=cfg["temperature"], sample=cfg["sample"], top_k=cfg["top_k"], **how)
+        for k, o in zip(picks, out.cpu().numpy()):
+            save_npy(o, cfg["outputs_directory"], files[k], "sample", np.uint16)
+    log(rank, f"inference done: {len(mine)} samples -> {cfg['outputs_directory']}")
 
 
 def run(argv):
@@ -170,6 +204,8 @@ def run(argv):
     cfg = parse_flags(argv, DEFAULTS, aliases={"n_embed": "n_embd"})
     if cfg["mode"] not in ("training", "inference"):
         raise ValueError(f"Transformer mode unknown. Was given {cfg['mode']} but choices are ['training', 'inference'].")
+    from synthanatomy_amd.utils.transformer import conditioning_flags
+    cfg["conditionings"] = conditioning_flags(cfg["conditioning_path"], cfg["conditionings"], cfg["conditioning_type"])   # they act or refuse: never ignored
     rank, local, world = init_distributed()
     cfg.update(rank=rank, local_rank=local, world_size=world)
     torch.manual_seed(cfg["seed"])

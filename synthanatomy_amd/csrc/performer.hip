@@ -26,10 +26,11 @@ static inline unsigned grid1d(int64_t n, int block = 256, unsigned cap = 8192) {
 }
 
 // ------------------------------------------------------------------------------------------------ embeddings
+#define SA_EMBED_MAX_TABLES 12   // token + 3 spatial + 2 axial positional + up to 6 conditioning tables
 struct EmbedArgs {
-    const float* table[6];
-    const int64_t* idx[6];
-    int32_t per_position[6];  // 1: index by position n = r % N (shared across the batch); 0: index by row r
+    const float* table[SA_EMBED_MAX_TABLES];
+    const int64_t* idx[SA_EMBED_MAX_TABLES];
+    int32_t per_position[SA_EMBED_MAX_TABLES];  // 1: index by position n = r % N (shared across the batch); 0: index by row r
     int32_t ntab, dim, N;
     int64_t R;
 };
@@ -2010,7 +2011,7 @@ using namespace sa;
 
 extern "C" int sa_embed_sum(int ntab, const float* const* tables, const int64_t* const* idx, const int32_t* per_position, int dim, int N, int64_t R,
                             float* out, void* stream) {
-    if (ntab < 1 || ntab > 6 || !tables || !idx || !per_position || !out || dim <= 0 || R <= 0) return SA_EINVAL;
+    if (ntab < 1 || ntab > SA_EMBED_MAX_TABLES || !tables || !idx || !per_position || !out || dim <= 0 || R <= 0) return SA_EINVAL;
     EmbedArgs a;
     for (int t = 0; t < ntab; ++t) {
         a.table[t] = tables[t];
@@ -2251,7 +2252,7 @@ extern "C" int sa_cross_entropy(const float* logits, const int64_t* target, int6
 
 extern "C" int sa_embed_step(int ntab, const float* const* tables, const int64_t* const* idx, const int32_t* per_position, int dim, const int* pos, int B,
                              float* out, void* stream) {
-    if (ntab < 1 || ntab > 6 || !tables || !idx || !per_position || !pos || !out || B <= 0) return SA_EINVAL;
+    if (ntab < 1 || ntab > SA_EMBED_MAX_TABLES || !tables || !idx || !per_position || !pos || !out || B <= 0) return SA_EINVAL;
     EmbedArgs a;
     a.ntab = ntab;
     a.dim = dim;

@@ -1126,6 +1126,50 @@ class _StackFn(torch.autograd.Function):
         return (None, None, dx, *[grads.get(p) for p in ctx.chain.params()])
 
 
+EMBED_MAX_TABLES = 12     # SA_EMBED_MAX_TABLES of csrc/performer.hip
+
+
+def conditioning_index_rows(conditioning_type: str, tok: torch.Tensor, sp: Sequence[torch.Tensor], conditionings: Sequence[torch.Tensor],
+                            shifted_sp: Optional[Sequence[torch.Tensor]] = None):
+    """Index rows that put the conditioning embeddings INTO the one embedding launch (``sa_embed_sum``: an index < 0 contributes nothing).
+
+    ``tok`` [B, N] token ids, ``sp`` the per-position spatial index rows [N] (-1 at position 0), ``conditionings`` c tensors [B] or [B, 1].  Returns
+    ``(tok_row [B * Nt], sp_rows [Nt] each, cond_rows [B * Nt] each, Nt)``; the positional indices are 0 .. Nt-1 in both cases.  Plain integer tensor
+    code on whatever device ``tok`` lives on (tests/test_conditioning_cpu.py asserts on the arrays).  ``shifted_sp``: the prepending form of ``sp`` when the
+    caller has it already (it depends on N and c only; ``Performer`` caches it); all c conditioning rows are written by one indexed assignment.
+
+    * ``bos_replacement`` (performer.py:252-261), Nt = N: position 0 loses its token (the spatial rows are -1 there already) and receives every conditioning
+      table's row instead: conditioning row i is -1 everywhere except ``[b, 0] = value_i[b]``.
+    * ``prepending`` (performer.py:262-264), Nt = c + N: token and spatial indices move back by c and are -1 on the c leading positions; conditioning i sits
+      at position c-1-i (the reference concatenates each one IN FRONT of the previous, so the last ends up first)."""
+    B, N = tok.shape
+    c = len(conditionings)
+    vals = [v.to(tok.device).long().reshape(B) for v in conditionings]
+    if conditioning_type == TransformerConditioningType.BOSREPLACEMENT.value:
+        nt = N
+        tok_row = tok.clone()
+        tok_row[:, 0] = -1
+        sp_rows = list(sp)
+        at = [0] * c
+    elif conditioning_type == TransformerConditioningType.PREPENDING.value:
+        nt = c + N
+        tok_row = torch.full((B, nt), -1, dtype=torch.int64, device=tok.device)
+        tok_row[:, c:] = tok
+        sp_rows = list(shifted_sp) if shifted_sp is not None else shift_spatial_rows(sp, c)
+        at = [c - 1 - i for i in range(c)]
+    else:
+        raise ValueError(f"conditionings were given but conditioning_type is {conditioning_type!r}")
+    rows = torch.full((c, B, nt), -1, dtype=torch.int64, device=tok.device)
+    rows[torch.arange(c, device=tok.device), :, torch.tensor(at, device=tok.device)] = torch.stack(vals)
+    cond_rows = [rows[i].view(-1) for i in range(c)]
+    return tok_row.contiguous().view(-1), sp_rows, cond_rows, nt
+
+
+def shift_spatial_rows(sp: Sequence[torch.Tensor], c: int):
+    """the per-position spatial index rows behind c prepended conditioning positions, which carry no spatial embedding (-1)"""
+    return [torch.cat((torch.full((c,), -1, dtype=torch.int64, device=r.device), r)) for r in sp]
+
+
 class _EmbedFn(torch.autograd.Function):
     """x[b,n,:] = sum of embedding rows (token, spatial x3 with a zero at position 0, absolute position) -- performer.py:241-266"""
 
@@ -1135,6 +1179,8 @@ class _EmbedFn(torch.autograd.Function):
         dim = tables[0].shape[1]
         out = torch.empty(B, N, dim, dtype=torch.float32, device=tables[0].device)
         n = len(tables)
+        if n > EMBED_MAX_TABLES:
+            raise ValueError(f"the embedding launch sums at most {EMBED_MAX_TABLES} tables, got {n} (token, spatial, positional and conditioning tables)")
         tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tables])
         ip = (ctypes.c_void_p * n)(*[i.data_ptr() for i in idx])
         pp = (ctypes.c_int32 * n)(*per_pos)
@@ -1381,17 +1427,19 @@ class Performer(TransformerBase):
     def sample(self, prefix: torch.Tensor, conditioning: torch.Tensor = None, temperature: float = 1.0, sample: bool = True, top_k: Optional[int] = None,
                stateful: Optional[bool] = None, use_graph: bool = True) -> torch.Tensor:
         """TransformerBase.sample (transformer.py:58-101).  ``stateful=False`` is the reference-faithful O(N^2) loop (a full forward over the
-        growing prefix per token); ``stateful=True`` (default without conditioning) carries the FAVOR+ running sums and the local-attention
-        key/value caches from token to token -- O(N), same logits up to fp32 rounding -- and replays one captured
-        HIP graph per token."""
+        growing prefix per token); ``stateful=True`` (default without conditioning and with BOS replacement) carries the FAVOR+ running sums and the
+        local-attention key/value caches from token to token -- O(N), same logits up to fp32 rounding -- and replays one
+        captured HIP graph per token.  Prepended conditionings decode statefully too when asked (``stateful=True``: the c conditioning positions are forced
+        entries in front of the prefix); their DEFAULT stays the reference loop."""
         bos = self.conditioning_type == TransformerConditioningType.BOSREPLACEMENT.value
-        if stateful is None:     # O(N) decoding unless the conditioning lengthens the sequence (prepending: the reference-faithful loop)
+        if stateful is None:     # O(N) decoding unless the conditioning lengthens the sequence (prepending: the reference-faithful loop unless asked)
             stateful = (conditioning is None or bos) and self.layer_pos_emb is None
         if stateful and self.layer_pos_emb is not None:
             raise NotImplementedError("stateful (O(N)) sampling does not rotate the global heads' q / k (rotary_position_emb=True): use stateful=False")
         if not stateful:
             return super().sample(prefix, conditioning=conditioning, temperature=temperature, sample=sample, top_k=top_k)
-        assert conditioning is None or bos, "stateful sampling takes BOS-replacement conditionings only (use stateful=False)"
+        assert not conditioning or self.conditioning_type != TransformerConditioningType.NONE.value, (
+            "stateful sampling takes conditionings only with conditioning_type 'bos_replacement' or 'prepending' (use stateful=False)")
         return self._sample_stateful(prefix, temperature, sample, top_k, use_graph, conditioning)
 
     def _sample_stateful(self, prefix, temperature, sample, top_k, use_graph, conditioning=None):
@@ -1401,24 +1449,35 @@ class Performer(TransformerBase):
         lib = _ffi.lib()
         B, P = prefix.shape
         steps = int(np.prod(self.ordering.dimensions))
-        total = P + steps                      # tokens in the final sequence; positions 0 .. total-2 are fed through the network
+        # Prepended conditionings (performer.py:262-264) are c forced entries in FRONT of the prefix: the internal sequence has c + P + steps entries, entry
+        # j < c embeds conditioning_emb[c-1-j](value) (the last conditioning comes first), and the kernels see a prefix of length c + P that they never
+        # overwrite.  BOS replacement (:252-261) and the unconditioned sampler are the case c = 0.
+        c = len(conditioning) if conditioning and self.conditioning_type == TransformerConditioningType.PREPENDING.value else 0
+        P += c
+        total = P + steps                      # entries of the internal sequence; positions 0 .. total-2 are fed through the network
         npos = total - 1
         assert npos <= self.max_seq_len, f"sequence length {npos} must be less than the max sequence length {self.max_seq_len}"
         seq = torch.zeros(B, total, dtype=torch.int64, device=dev)
-        seq[:, :P] = prefix.to(dev).long()
-        seq0 = seq.clone()
+        seq[:, c:P] = prefix.to(dev).long()
         posbuf = torch.zeros(2, dtype=torch.int32, device=dev)     # [position, ticket word of sa_sample_step]
         pos, ticket = posbuf[:1], posbuf[1:]
         tok = torch.zeros(B, dtype=torch.int64, device=dev)
-        pidx, sp = self._position_indices(npos, dev)
+        pidx, sp = self._position_indices(npos - c, dev)
+        if c:                                  # spatial index rows move back by c; the positional indices run 0 .. c + total - 2
+            sp, pidx = self._prepended_indices(npos - c, c, dev)
         tok_table = self.token_emb.weight
         if conditioning:
-            # BOS replacement (performer.py:252-261): position 0 carries the summed conditioning embeddings instead of its token (+ spatial, which are zero
-            # there) embedding -> B extra rows behind the token table, and position 0 of sequence b points at row num_tokens + b
-            c = sum(emb(conditioning[i].to(dev))[:, 0, :] for i, emb in enumerate(self.conditioning_emb))
-            tok_table = torch.cat((self.token_emb.weight.detach(), c.to(self.token_emb.weight.dtype)), dim=0).contiguous()
-            seq[:, 0] = tok_table.shape[0] - B + torch.arange(B, device=dev)
-            seq0 = seq.clone()
+            assert len(conditioning) == len(self.conditioning_emb), f"{len(self.conditioning_emb)} conditioning tables but {len(conditioning)} conditionings"
+            # extra rows behind the token table, and the forced entries of sequence b point at them.  BOS replacement: B rows, position 0 carries the summed
+            # conditioning embeddings instead of its token (+ spatial, which are zero there) embedding.  Prepending: c * B rows, entry j of sequence b is
+            # row num_tokens + j * B + b = conditioning_emb[c-1-j](value_b).
+            cemb = [emb(conditioning[i].to(dev).long().reshape(B)) for i, emb in enumerate(self.conditioning_emb)]
+            extra = [cemb[c - 1 - j] for j in range(c)] if c else [sum(cemb)]
+            tok_table = torch.cat([self.token_emb.weight.detach()] + [e.to(self.token_emb.weight.dtype) for e in extra], dim=0).contiguous()
+            first = self.token_emb.weight.shape[0] + torch.arange(B, device=dev)
+            for j in range(max(c, 1)):
+                seq[:, j] = first + j * B
+        seq0 = seq.clone()
         ptabs, pidxs = self._pos_tables(pidx)
         tables = [tok_table] + [(m.emb if isinstance(m, FixedSpatialPositionalEmbedding) else m.emb.weight) for m in self.spatial_position_emb] + ptabs
         idx = [tok] + sp + pidxs
@@ -1511,7 +1570,7 @@ class Performer(TransformerBase):
                 graph.replay()
             else:
                 one_step()
-        return sequence_to_grid(seq, P, self.ordering)
+        return sequence_to_grid(seq[:, c:], P - c, self.ordering)
 
     # ------------------------------------------------------------------------------------------------
     def _pos_table(self):
@@ -1525,11 +1584,6 @@ class Performer(TransformerBase):
             return ([self.pos_emb.weights_0.view(s0, self.dim), self.pos_emb.weights_1.view(s1, self.dim)],
                     [torch.div(pos, s1, rounding_mode="floor"), pos % s1])
         return [self._pos_table()], [pos]
-
-    def _pos_rows(self, n, dev):
-        """the positional term of positions 0 .. n-1 as a dense [n, dim] tensor (autograd-visible): the conditioning paths add single rows of it"""
-        tabs, idx = self._pos_tables(torch.arange(n, device=dev, dtype=torch.int64))
-        return sum(t[i] for t, i in zip(tabs, idx))
 
     def _position_indices(self, n, dev):
         key = (n, str(dev))
@@ -1551,6 +1605,14 @@ class Performer(TransformerBase):
             self._idx_cache[key] = (pos, sp)
         return self._idx_cache[key]
 
+    def _prepended_indices(self, n, c, dev):
+        """(spatial index rows moved back by c, positional indices 0 .. c+n-1) of a sequence of n tokens behind c prepended conditionings; cached like
+        ``_position_indices``: they depend on (n, c) only"""
+        key = ("prepended", n, c, str(dev))
+        if key not in self._idx_cache:
+            self._idx_cache[key] = (shift_spatial_rows(self._position_indices(n, dev)[1], c), torch.arange(c + n, device=dev, dtype=torch.int64))
+        return self._idx_cache[key]
+
     def forward(self, x: torch.Tensor, conditionings: Sequence[torch.Tensor] = None, return_encodings: bool = False, **kwargs):
         b, n = x.shape
         assert n <= self.max_seq_len, f"sequence length {n} must be less than the max sequence length {self.max_seq_len}"
@@ -1559,29 +1621,28 @@ class Performer(TransformerBase):
         pos, sp = self._position_indices(n, dev)
         sp_tables = [(m.emb if isinstance(m, FixedSpatialPositionalEmbedding) else m.emb.weight) for m in self.spatial_position_emb]
         prepend = bool(conditionings) and self.conditioning_type == TransformerConditioningType.PREPENDING.value
-        if prepend:
-            # performer.py:262-266: token + spatial embeddings, THEN the conditioning embeddings in front (the last one ends up first), THEN the
-            # absolute positional embedding over the longer sequence; the conditioning positions are cut off again after the final norm (:279-281)
-            tables, idx, per_pos = [self.token_emb.weight] + sp_tables, [tok] + sp, [0] + [1] * len(sp)
-            h = _EmbedFn.apply(tables, idx, per_pos, b, n, *tables)
-            for i, emb in enumerate(self.conditioning_emb):
-                h = torch.cat((emb(conditionings[i].to(dev)), h), dim=1)
-            nt = h.shape[1]
+        if conditionings and self.conditioning_type != TransformerConditioningType.NONE.value:
+            # BOS replacement (performer.py:252-261: the BOS embedding incl. its spatial terms is REPLACED by the summed conditioning embeddings, the positional
+            # embedding is added afterwards) and prepending (:262-266: the conditioning embeddings in front, the last one first, THEN the positional embedding
+            # over the longer sequence; the conditioning positions are cut off again after the final norm, :279-281) as index rows of the SAME launch: the
+            # conditioning tables join with per-row indices that are -1 outside their position, and their gradients come from _EmbedFn.backward like the others'
+            assert len(conditionings) == len(self.conditioning_emb), f"{len(self.conditioning_emb)} conditioning tables but {len(conditionings)} conditionings"
+            nt = n + (len(conditionings) if prepend else 0)
             assert nt <= self.max_seq_len, f"sequence length {nt} must be less than the max sequence length {self.max_seq_len}"
-            ptab, pix = self._pos_tables(torch.arange(nt, device=dev, dtype=torch.int64))
-            h = h + _EmbedFn.apply(ptab, pix, [1] * len(ptab), b, nt, *ptab)
+            shifted, pos = self._prepended_indices(n, len(conditionings), dev) if prepend else (None, pos)
+            tok, sp, crows, nt = conditioning_index_rows(self.conditioning_type, tok.view(b, n), sp, conditionings, shifted)
+            ptab, pix = self._pos_tables(pos)
+            ctabs = [emb.weight for emb in self.conditioning_emb]
+            tables = [self.token_emb.weight] + sp_tables + ctabs + ptab
+            idx = [tok] + sp + crows + pix
+            per_pos = [0] + [1] * len(sp) + [0] * len(ctabs) + [1] * len(ptab)
+            h = _EmbedFn.apply(tables, idx, per_pos, b, nt, *tables)
         else:
             ptab, pix = self._pos_tables(pos)
             tables = [self.token_emb.weight] + sp_tables + ptab
             idx = [tok] + sp + pix
             per_pos = [0] + [1] * len(sp) + [1] * len(ptab)
             h = _EmbedFn.apply(tables, idx, per_pos, b, n, *tables)
-        if conditionings and self.conditioning_type == TransformerConditioningType.BOSREPLACEMENT.value:
-            # performer.py:252-261: the BOS embedding (incl. its spatial terms) is REPLACED by the summed conditioning embeddings,
-            # the absolute positional embedding is added afterwards
-            c = sum(emb(conditionings[i].to(dev))[:, 0, :] for i, emb in enumerate(self.conditioning_emb))
-            first = c + self._pos_rows(1, dev)[0]
-            h = torch.cat((first[:, None, :], h[:, 1:, :]), dim=1)
         if self.dropout.p > 0.0 and self.training:
             # nn.Dropout(emb_dropout) on the summed embeddings (performer.py:201,270): elementwise keep / (1 - p) mask drawn on the device, a broadcast-free multiply
             keep = torch.bernoulli(torch.full_like(h, 1.0 - self.dropout.p)) / (1.0 - self.dropout.p)
