@@ -260,6 +260,32 @@ typedef struct sa_augment_params {
 int sa_augment(const float *x, float *y, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, const sa_augment_params *params, uint64_t seed, void *ws,
                void *stream);
 int64_t sa_augment_workspace_bytes(int B);
+/* NIfTI-1 voxel block -> fp32 volume in canonical (RAS+) axes (reference src/utils/vqvae.py:205-215: LoadImaged(as_closest_canonical) / AddChanneld /
+ * ScaleIntensityd(0, 1) / the ROI crop; run_vqvae.py with .nii / .nii.gz inputs; csrc/ingest.hip).  raw: the voxel block as stored, in device
+ * memory, 16-byte aligned, raw_bytes long; file dims n = (n0, n1, n2) with axis 0 FASTEST (file offset i0 + n0 (i1 + n1 i2)), dtype a NIfTI datatype
+ * code below, byteswap != 0 for a big-endian file.  y [ext0][ext1][ext2] fp32 contiguous (the last axis fastest).  params is read on the HOST.
+ * Canonical axis a reads file axis perm[a], n_can[a] = n[perm[a]].  For an output voxel o the canonical voxel is c = off + o and the file index along
+ * axis perm[a] is c_a, or n_can[a] - 1 - c_a where sign[a] < 0 (SA_AUG_SIGNED_PERM's convention).  Value: float(raw) when (slope, inter) == (1, 0), else
+ * float(double(raw) * slope + inter) as two rounded double operations.  A non-finite value becomes 0, is counted, and takes no part in min / max.  With
+ * SA_INGEST_NORMALIZE: y = (v - min) / ((max - min) + 1e-8f) in fp32, min / max over the WHOLE volume, not the window (the scaling runs before the crop).
+ * At most two launches on the stream, no host synchronisation.  ws: sa_volume_ingest_workspace_bytes() bytes, 8-byte aligned, ZERO before its first
+ * use and then left alone between calls (one call at a time per workspace): 64-bit words [0], [1] reduction keys, [2] = the float min (low half) and max
+ * (high half) of the finite voxels (0, 0 without one), [3] = status: the number of non-finite voxels, [4], [5] internal; the call resets all but [2], [3].
+ * SA_EINVAL (nothing launched) for null operands, a misaligned raw, a dim or an extent < 1, a window outside the canonical dims, a perm that is no
+ * permutation, raw_bytes smaller than the dims need; SA_EUNSUPPORTED for an unknown dtype and for n0 n1 n2 >= 2^31 - 16. */
+enum { SA_NII_UINT8 = 2, SA_NII_INT16 = 4, SA_NII_INT32 = 8, SA_NII_FLOAT32 = 16, SA_NII_FLOAT64 = 64, SA_NII_INT8 = 256, SA_NII_UINT16 = 512,
+       SA_NII_UINT32 = 768 };
+enum { SA_INGEST_NORMALIZE = 1 };
+typedef struct sa_ingest_params {
+    int32_t dtype, byteswap;
+    int32_t n[3];
+    int32_t perm[3], sign[3];
+    int32_t off[3], ext[3];
+    int32_t flags;
+    double slope, inter;
+} sa_ingest_params; /* 88 bytes */
+int sa_volume_ingest(const void *raw, int64_t raw_bytes, float *y, const sa_ingest_params *params, void *ws, void *stream);
+int64_t sa_volume_ingest_workspace_bytes(void);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

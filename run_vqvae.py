@@ -10,7 +10,10 @@ spectral convergence + log magnitude; their factors are not scheduled, as upstre
 by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_factor_value; the LPIPS family is out of scope), optional adversarial component
 (src/engines/trainer.py semantics incl. the adaptive weight; criteria vanilla / hinge / least_square), checkpoints with the reference's keys
 (network, optimizer, lr_scheduler, trainer, d_*) restored on resume, uint16 ``.npy`` code files.
-Inputs: ``.npy`` volumes (any of dir / glob / csv listing) or ``synthetic:<n>`` (uniform [0,1) volumes of ``--roi`` size).
+Inputs: ``.npy`` volumes, single-file NIfTI-1 volumes (``.nii`` / ``.nii.gz``: read with the standard library, then converted, reoriented to the
+closest canonical axes with ``--load_nii_canonical``, scaled to [0, 1] with ``--normalize`` and cropped to ``--roi`` on the device by ``sa_volume_ingest``,
+DESIGN 7.7; ``--num_workers`` threads read the next batch's files ahead) -- any of dir / glob / csv listing -- or ``synthetic:<n>`` (uniform [0,1)
+volumes of ``--roi`` size).
 Multi-GPU: launch with torchrun; one process per GPU, RCCL.
 
 ``--augmentation=True`` (MI355X-only switch, default False) turns on the reference's training augmentations (src/utils/vqvae.py:183-371, which upstream
@@ -51,14 +54,18 @@ def _roi_shape(cfg):
     return tuple(int(b - a) for a, b in cfg["roi"])
 
 
-def _load_volume(path, cfg, gen, dev):
+def _load_volume(path, cfg, gen, dev, block=None):
     if path.startswith("synthetic"):   # a volume that depends on its NAME only (not on how many were drawn before it): resumable, rank-independent
         g = torch.Generator(device=dev).manual_seed(cfg["seed"] * 1000003 + int(path.split("_")[-1]))
         return torch.rand(1, *_roi_shape(cfg), generator=g, device=dev)
+    if _is_nifti(path):
+        return _nifti_volume(path, cfg, dev, block)[0]
     return _read_volume(path, cfg).to(dev)
 
 
-def _read_volume(path, cfg):
+def _read_volume(path, cfg, dev=None, block=None):
+    if _is_nifti(path):                # the whole volume in canonical axes, converted and normalised by sa_volume_ingest (there is no host decoder)
+        return _nifti_volume(path, dict(cfg, roi=None), dev, block)[0].cpu()
     v = torch.from_numpy(np.load(path).astype(np.float32))
     if v.dim() == 3:
         v = v[None]
@@ -67,11 +74,57 @@ def _read_volume(path, cfg):
     return v
 
 
+def _is_nifti(path):
+    return path.endswith((".nii", ".nii.gz"))
+
+
+def _nifti_volume(path, cfg, dev, block=None, whole=False):
+    """A NIfTI-1 volume through sa_volume_ingest and where the ROI starts inside what is returned: LoadImaged(as_closest_canonical =
+    --load_nii_canonical), ScaleIntensityd(0, 1) over the whole volume with --normalize, then the ROI as the kernel's window (``whole``: the whole canonical
+    volume and the ROI's start, for sa_augment to crop).  A file smaller than the ROI is ingested whole, cropped and mirror-padded on the host (the rare
+    path of ``_load_input``).  ``block`` = (header, voxel block) when a worker has read the file already."""
+    from synthanatomy_amd.utils.nifti import header_orientation, read_nifti
+    from synthanatomy_amd.utils.vqvae import hip_ingest, pad_to_roi, roi_shape, roi_window
+    header, raw = block if block is not None else read_nifti(path)
+    canonical = bool(cfg.get("load_nii_canonical", True))
+    kw = dict(normalize=bool(cfg["normalize"]), canonical=canonical, device=dev)
+    if not cfg["roi"]:
+        return hip_ingest(header, raw, None, **kw), [0, 0, 0]
+    start, size = roi_window(cfg["roi"], [header.dims[k] for k in header_orientation(header, canonical)[0]])
+    if size != roi_shape(cfg["roi"]):
+        v = hip_ingest(header, raw, None, **kw)
+        crop = v[..., start[0]:start[0] + size[0], start[1]:start[1] + size[1], start[2]:start[2] + size[2]].cpu().numpy()
+        return torch.from_numpy(np.ascontiguousarray(pad_to_roi(crop, cfg["roi"]))).to(v.device), [0, 0, 0]
+    if whole:
+        return hip_ingest(header, raw, None, **kw), start
+    return hip_ingest(header, raw, (start, size), **kw), [0, 0, 0]
+
+
+def _with_nifti_blocks(chunks, path_of, cfg):
+    """(chunk, blocks) for every chunk, ``blocks[j]`` = (header, voxel block) of the chunk's j-th file when it is a NIfTI file, else None.  File read and
+    gunzip are host work that releases the GIL: with ``--num_workers`` > 0 the NEXT chunk's files are fetched on min(num_workers, 8) threads while the
+    caller works on the current one; 0 reads inline.  Order and content do not depend on the worker count."""
+    from synthanatomy_amd.utils.nifti import read_nifti
+    workers = min(int(cfg.get("num_workers") or 0), 8)
+    if workers <= 0 or not any(_is_nifti(path_of(it)) for c in chunks for it in c):
+        for c in chunks:
+            yield c, [read_nifti(path_of(it)) if _is_nifti(path_of(it)) else None for it in c]
+        return
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(workers) as ex:
+        def submit(c):
+            return [ex.submit(read_nifti, path_of(it)) if _is_nifti(path_of(it)) else None for it in c]
+        ahead = submit(chunks[0])
+        for i, c in enumerate(chunks):
+            current, ahead = ahead, (submit(chunks[i + 1]) if i + 1 < len(chunks) else None)
+            yield c, [f.result() if f is not None else None for f in current]
+
+
 def _batches(files, order, bs, cfg, gen, dev):
     """Batches of this rank's shard (``order`` = indices into ``files`` from utils.general.shard_for_rank)."""
-    for i in range(0, len(order), bs):
-        chunk = [files[k] for k in order[i:i + bs]]
-        yield chunk, torch.stack([_load_volume(f, cfg, gen, dev) for f in chunk])
+    chunks = [[files[k] for k in order[i:i + bs]] for i in range(0, len(order), bs)]
+    for chunk, blocks in _with_nifti_blocks(chunks, lambda f: f, cfg):
+        yield chunk, torch.stack([_load_volume(f, cfg, gen, dev, b) for f, b in zip(chunk, blocks)])
 
 
 def _noise_seed(seed, counter, stream=0):
@@ -83,10 +136,12 @@ def _noise_seed(seed, counter, stream=0):
     return z ^ (z >> 31)
 
 
-def _load_input(path, cfg, dev):
+def _load_input(path, cfg, dev, block=None):
     """A volume for the sa_augment path and where the ROI starts inside it: the kernel crops (CenterSpatialCropd for three ints, SpatialCropd for three
     pairs); a file smaller than the ROI is cropped and mirror-padded on the host first (SpatialPadd SYMMETRIC, the rare path)."""
     from synthanatomy_amd.utils.vqvae import pad_to_roi, roi_shape, roi_window
+    if _is_nifti(path):
+        return _nifti_volume(path, cfg, dev, block, whole=True)
     if path.startswith("synthetic") or not cfg["roi"]:
         return _load_volume(path, cfg, None, dev), [0, 0, 0]
     v = _read_volume(path, cfg)
@@ -101,10 +156,11 @@ def _augmented_batches(items, bs, cfg, dev, mode, noise_seed):
     """Batches through sa_augment.  ``items``: (output name, file, epoch key, subject index) -- the draws of a sample depend on (--seed, epoch key, subject
     index) only (synthanatomy_amd.utils.vqvae.draw_augmentation); ``noise_seed(k)`` is the noise seed of batch k.  Yields (names, batch, noise seed)."""
     from synthanatomy_amd.utils.vqvae import draw_augmentation, hip_augment, in_window, roi_shape
-    for i in range(0, len(items), bs):
-        chunk, vols, recs = items[i:i + bs], [], []
-        for _, f, epoch_key, subject in chunk:
-            v, start = _load_input(f, cfg, dev)
+    chunks = [items[i:i + bs] for i in range(0, len(items), bs)]
+    for i, (chunk, blocks) in zip(range(0, len(items), bs), _with_nifti_blocks(chunks, lambda it: it[1], cfg)):
+        vols, recs = [], []
+        for (_, f, epoch_key, subject), block in zip(chunk, blocks):
+            v, start = _load_input(f, cfg, dev, block)
             dims = roi_shape(cfg["roi"]) if cfg["roi"] else list(v.shape[-3:])
             recs.append(in_window(draw_augmentation(cfg, mode, cfg["seed"], epoch_key, subject, dims), start))
             vols.append(v)

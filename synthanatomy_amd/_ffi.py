@@ -59,6 +59,12 @@ class LocalAttnArgs(Structure):
                 ("L", c_int32), ("W", c_int32)]
 
 
+class IngestParams(Structure):
+    """sa_ingest_params (include/synthanatomy_hip.h): read on the host by sa_volume_ingest."""
+    _fields_ = [("dtype", c_int32), ("byteswap", c_int32), ("n", c_int32 * 3), ("perm", c_int32 * 3), ("sign", c_int32 * 3), ("off", c_int32 * 3),
+                ("ext", c_int32 * 3), ("flags", c_int32), ("slope", ctypes.c_double), ("inter", ctypes.c_double)]
+
+
 _SIGS = {
     "sa_abi_version": (c_int, []),
     "sa_last_error": (c_char_p, []),
@@ -106,6 +112,8 @@ _SIGS = {
     "sa_ms_ssim_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sa_augment": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
     "sa_augment_workspace_bytes": (c_int64, [c_int]),
+    "sa_volume_ingest": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sa_volume_ingest_workspace_bytes": (c_int64, []),
     "sa_bn_sums_ws_floats": (c_int64, [c_int]),
     "sa_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "sa_embed_sum": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p]),

@@ -246,7 +246,7 @@ def save_npy(array, output_dir: str, filename: str, postfix: str, dtype=np.uint1
 
 
 def list_inputs(spec, postfix: str = None):
-    """A directory, a glob, a .csv/.tsv whose first column lists files, or 'synthetic:<n>'.  ``postfix`` filters a DIRECTORY listing to
+    """A directory (its ``.npy``, ``.nii`` and ``.nii.gz`` files), a glob, a .csv/.tsv whose first column lists files, or 'synthetic:<n>'.  ``postfix`` filters a DIRECTORY listing to
     ``*_<postfix>.npy`` -- the extraction stage writes codes (``quantization_0``) and fp32 reconstructions side by side, and the next stage
     must only pick up its own kind."""
     if isinstance(spec, (tuple, list)):
@@ -255,7 +255,7 @@ def list_inputs(spec, postfix: str = None):
         n = int(spec.split(":")[1]) if ":" in spec else 8
         return [f"synthetic_{i:04d}" for i in range(n)]
     if os.path.isdir(spec):
-        found = sorted(glob.glob(os.path.join(spec, "**", "*.npy"), recursive=True))
+        found = sorted(f for ext in ("*.npy", "*.nii", "*.nii.gz") for f in glob.glob(os.path.join(spec, "**", ext), recursive=True))
         if postfix is not None and any(f.endswith(f"_{postfix}.npy") for f in found):
             found = [f for f in found if f.endswith(f"_{postfix}.npy")]
         return found

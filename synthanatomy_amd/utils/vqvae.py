@@ -231,6 +231,47 @@ def hip_augment(x, records: np.ndarray, out_dims, seed: int, return_workspace: b
     return (y, ws[:4 * B].view(B, 4)) if return_workspace else y
 
 
+INGEST_NORMALIZE = 1      # include/synthanatomy_hip.h: SA_INGEST_NORMALIZE
+_INGEST_WS = {}           # device index -> zeroed workspace (sa_volume_ingest resets it)
+
+
+def hip_ingest(header, raw, window=None, normalize: bool = True, canonical: bool = True, device=None, return_workspace: bool = False):
+    """``sa_volume_ingest``: the voxel block ``raw`` of a NIfTI-1 file (``utils.nifti.read_nifti``) -> [1, *ext] fp32 on the device in canonical axes (the
+    stored order without ``canonical``).  ``window`` = (start, size) in those axes, None = the whole volume; ``normalize`` = ScaleIntensityd(0, 1) over the
+    WHOLE volume.  One upload of the block as stored, at most two launches on the current stream.  ``return_workspace``: also the int64 view of the
+    workspace (word 2 = the float min | max << 32 of the finite voxels, word 3 = the number of non-finite voxels, which came out as 0)."""
+    import ctypes
+    import warnings
+
+    import torch
+    from .. import _ffi
+    from .nifti import header_orientation
+    _ffi.require_gpu()
+    perm, sign = header_orientation(header, canonical)
+    n_can = [int(header.dims[k]) for k in perm]
+    start, size = ([0, 0, 0], n_can) if window is None else ([int(v) for v in window[0]], [int(v) for v in window[1]])
+    if len(start) != 3 or len(size) != 3 or any(s < 0 or e < 1 or s + e > n for s, e, n in zip(start, size, n_can)):
+        raise ValueError(f"hip_ingest: window start {start} size {size} does not fit the volume {tuple(n_can)} of {header.path}")
+    if len(raw) < header.nbytes:
+        raise ValueError(f"hip_ingest: {header.path}: the voxel block holds {len(raw)} bytes, dims {tuple(header.dims)} need {header.nbytes}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)      # (a read-only buffer: it is only read)
+        block = torch.frombuffer(raw, dtype=torch.uint8, count=header.nbytes).to(dev)
+    lib = _ffi.lib()
+    ws = _INGEST_WS.get(dev.index)
+    if ws is None:
+        ws = _INGEST_WS[dev.index] = torch.zeros(8, dtype=torch.int64, device=dev)
+    assert lib.sa_volume_ingest_workspace_bytes() <= ws.numel() * 8
+    P = _ffi.IngestParams(dtype=header.datatype, byteswap=int(header.byteswap), flags=INGEST_NORMALIZE if normalize else 0, slope=header.slope,
+                          inter=header.inter)
+    P.n[:], P.perm[:], P.sign[:], P.off[:], P.ext[:] = [int(v) for v in header.dims], perm, sign, start, size
+    y = torch.empty((1, *size), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(lib.sa_volume_ingest(_ffi.ptr(block), header.nbytes, _ffi.ptr(y), ctypes.byref(P), _ffi.ptr(ws), _ffi.stream()), "sa_volume_ingest")
+    return (y, ws) if return_workspace else y
+
+
 def get_ms_ssim_window(config: dict, logger=None) -> int:
     """Window size of the MS-SSIM key metric (reference ``src/utils/vqvae.py:499-543``).  The smallest spatial side comes from ``eval_patch_size``,
     else from ``roi`` (ints or (start, stop) pairs), else from ``input_shape``.  A side > 160 gives 11; otherwise w = floor((side / 16 + 1) / 2),
