@@ -286,6 +286,37 @@ typedef struct sa_ingest_params {
 } sa_ingest_params; /* 88 bytes */
 int sa_volume_ingest(const void *raw, int64_t raw_bytes, float *y, const sa_ingest_params *params, void *ws, void *stream);
 int64_t sa_volume_ingest_workspace_bytes(void);
+/* fp32 / bf16 volume in canonical axes -> NIfTI-1 voxel block as stored: the inverse of sa_volume_ingest (reference run_vqvae.py:467-514:
+ * SegmentationSaver(output_ext=".nii.gz", resample=False, dtype=float32) of --mode=extracting / decoding; run_vqvae.py --output_ext; csrc/egress.hip,
+ * DESIGN 7.8).  x [ext0][ext1][ext2] contiguous device tensor (the last axis fastest) of x_dtype, in canonical axes; raw: device memory, 16-byte aligned,
+ * raw_bytes long, receives the voxel block, always little-endian.  params is read on the HOST.  File dims n[perm[a]] = ext[a]; the file is axis-0-FASTEST
+ * (offset i0 + n0 (i1 + n1 i2)).  File voxel i takes x[c] with c_a = i[perm[a]], or ext[a] - 1 - i[perm[a]] where sign[a] < 0 (sa_ingest_params'
+ * convention: an ingest of the block with the same perm / sign gives x back).  No offset, no fill, no byte swap.
+ * Value: SA_NII_FLOAT32 stores float(x) (a bf16 input widens exactly).  SA_NII_INT16 / SA_NII_UINT8 store q = rint((double(v) - inter) / slope) -- the
+ * subtraction and the division are two rounded double operations, rint rounds half to even -- clamped to the type's range [tmin, tmax].  A non-finite
+ * input is stored as 0.0f (float32) or as the code of the value 0.0 (integers), is counted, and takes no part in min / max.
+ * SA_EGRESS_AUTOSCALE (integer dtypes only; ignored for float32): two launches, a min / max reduction and the conversion, which reads its pair on the
+ * device.  The pair covers [min, max] with the full code range and both numbers are float32 values, because a NIfTI header stores them as float32 and a
+ * reader applies the rounded ones:  slope = float32((max - min) / (tmax - tmin)), computed in double and moved to the next float32 up when
+ * double(slope) * (tmax - tmin) < max - min;  inter = float32(min - tmin * slope) computed in double;  max <= min (a constant volume, or no finite
+ * voxel: min = max = 0) gives slope = 1, inter = min.  Without the flag one launch, with the caller's (slope, inter) for integer dtypes.
+ * ws: sa_volume_egress_workspace_bytes() = 64 bytes, 8-byte aligned, ZERO before its first use and then left alone between calls (one call at a time per
+ * workspace): 64-bit words [0], [1] reduction keys, [2] = the float min (low half) and max (high half) of the finite voxels (0, 0 without one), [3] = the
+ * number of non-finite voxels, [4], [5] internal, [6], [7] = the bits of the doubles (slope, inter) the conversion used ((1, 0) for float32); the call
+ * resets all but [2], [3], [6], [7].  No host synchronisation.
+ * SA_EINVAL (nothing launched) for null operands, a misaligned raw, an extent < 1, a perm that is no permutation, raw_bytes smaller than the dims need,
+ * and a zero or non-finite (slope, inter) given for an integer dtype; SA_EUNSUPPORTED for another dtype or x_dtype and for ext0 ext1 ext2 >= 2^31 - 16. */
+enum { SA_EGRESS_AUTOSCALE = 1 };
+typedef struct sa_egress_params {
+    int32_t x_dtype;            /* SA_F32 = 0 | SA_BF16 = 1 */
+    int32_t dtype;              /* SA_NII_FLOAT32 | SA_NII_INT16 | SA_NII_UINT8 */
+    int32_t ext[3];
+    int32_t perm[3], sign[3];
+    int32_t flags;              /* SA_EGRESS_AUTOSCALE */
+    double slope, inter;        /* integer dtypes without SA_EGRESS_AUTOSCALE */
+} sa_egress_params; /* 64 bytes */
+int sa_volume_egress(const void *x, void *raw, int64_t raw_bytes, const sa_egress_params *params, void *ws, void *stream);
+int64_t sa_volume_egress_workspace_bytes(void);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -23,6 +23,15 @@ Gaussian noise and the clamp to [0, 1].  Training batches AND the evaluator's ba
 device in two launches of ``sa_augment``; the draws are keyed on (seed, epoch, subject), the noise on (seed, iteration).  With the default
 False the loop is untouched and ``--augmentation_probability`` stays inert.  ``--patch_size`` crops training batches with or without the switch, and
 ``--mode=extracting --no_augmented_extractions=n`` writes n augmented extractions ``<name>_<i>`` per subject (no switch needed, as upstream).
+
+``--output_ext=.npy|.nii|.nii.gz`` and ``--output_dtype=float32|int16|uint8`` (MI355X-only switches, defaults ``.npy`` / ``float32``: nothing changes for
+existing runs) write the volumes of ``--mode=extracting`` (``<name>_reconstruction``) and ``--mode=decoding`` (``<name>_sample``) as single-file NIfTI-1,
+what upstream's ``SegmentationSaver(output_ext=".nii.gz", resample=False, dtype=float32)`` produces (reference run_vqvae.py:467-514).  The voxel block is
+made on the device by ``sa_volume_egress`` straight from the decoder's output: a reconstruction of a NIfTI input goes back into its source
+file's own axes with an affine that puts the ROI where the source has it; other inputs and every decoded sample get the identity.  Integer dtypes are
+auto-scaled to the full code range (scl_slope / scl_inter in the header).  ``--num_workers`` threads (at most 8) compress and write while the next batch
+is decoded.  The code files stay uint16 ``.npy``.  The flags act or refuse: an unknown value, an integer dtype with ``.npy``, a NIfTI extension with
+``--mode=training`` or with ``--no_augmented_extractions > 0`` raise a ``ValueError`` before anything runs.
 """
 import os
 import sys
@@ -47,7 +56,33 @@ DEFAULTS = dict(
     downsample_parameters=((4, 2, 1, 1),) * 3, upsample_parameters=((4, 2, 1, 0, 1),) * 3, no_res_layers=3, no_channels=256, codebook_type="ema",
     num_embeddings=(256,), embedding_dim=(256,), embedding_init=("normal",), commitment_cost=(0.25,), decay=(0.99,), decay_warmup=None,
     max_decay_epochs=50, norm=None, dropout=0.0, act="RELU", output_act=None, evaluation_checkpoint="recent", load_nii_canonical=True,
+    output_ext=".npy", output_dtype="float32",
 )
+
+
+def _check_output_flags(cfg):
+    """--output_ext / --output_dtype act or refuse (before anything touches the device)."""
+    ext, dt, n_aug = cfg["output_ext"], cfg["output_dtype"], int(cfg["no_augmented_extractions"] or 0)
+    if ext not in (".npy", ".nii", ".nii.gz"):
+        raise ValueError(f"--output_ext={ext}: choices are .npy, .nii and .nii.gz")
+    if dt not in ("float32", "int16", "uint8"):
+        raise ValueError(f"--output_dtype={dt}: choices are float32, int16 and uint8")
+    if ext == ".npy" and dt != "float32":
+        raise ValueError(f"--output_dtype={dt} needs a NIfTI --output_ext (.nii or .nii.gz): .npy outputs are float32")
+    if ext != ".npy" and cfg["mode"] == "training":
+        raise ValueError(f"--output_ext={ext}: --mode=training writes no volumes (the flag belongs to --mode=extracting and --mode=decoding)")
+    if ext != ".npy" and n_aug > 0:
+        raise ValueError(f"--output_ext={ext} with --no_augmented_extractions={n_aug}: augmented extractions are not on the source grid and exist for "
+                         "their codes; leave --output_ext at .npy")
+
+
+def _output_path(cfg, filename, postfix):
+    """``<outputs>/<name>/<name>_<postfix><--output_ext>``: utils.general.save_npy's layout."""
+    name = os.path.basename(filename)
+    for ext in (".nii.gz", ".nii", ".npy"):
+        if name.endswith(ext):
+            name = name[:-len(ext)]
+    return os.path.join(cfg["outputs_directory"], name, f"{name}_{postfix}{cfg['output_ext']}")
 
 
 def _roi_shape(cfg):
@@ -124,7 +159,8 @@ def _batches(files, order, bs, cfg, gen, dev):
     """Batches of this rank's shard (``order`` = indices into ``files`` from utils.general.shard_for_rank)."""
     chunks = [[files[k] for k in order[i:i + bs]] for i in range(0, len(order), bs)]
     for chunk, blocks in _with_nifti_blocks(chunks, lambda f: f, cfg):
-        yield chunk, torch.stack([_load_volume(f, cfg, gen, dev, b) for f, b in zip(chunk, blocks)])
+        headers = [b[0] if b is not None else None for b in blocks]      # the NIfTI headers already read (utils.vqvae.nifti_output_geometry); None for other inputs
+        yield chunk, torch.stack([_load_volume(f, cfg, gen, dev, b) for f, b in zip(chunk, blocks)]), headers
 
 
 def _noise_seed(seed, counter, stream=0):
@@ -343,30 +379,52 @@ def inference(cfg, rank, local, world, dev):
         log(rank, f"loaded {path}")
     gen = torch.Generator(device=dev).manual_seed(cfg["seed"] + rank)
     files = list_inputs(cfg["validation_subjects"] if cfg["mode"] == "extracting" else cfg["training_subjects"])
-    with torch.no_grad():
-        if cfg["mode"] == "extracting":
-            order = shard_for_rank(len(files), rank, world, shuffle=False, pad=False)   # even_divisible=False: no duplicates, no collectives
-            n_aug = int(cfg["no_augmented_extractions"] or 0)
-            if n_aug > 0:      # every subject n_aug times, augmentation_id i drawn as "epoch" i (reference src/utils/vqvae.py:126-181,194-196)
-                batches = _augmented_batches([(_augmented_name(files[k], i), files[k], i, k) for k in order for i in range(n_aug)], cfg["eval_batch_size"], cfg,
-                                             dev, "extracting", lambda k: _noise_seed(cfg["seed"], k * world + rank, 2))
-            else:
-                batches = _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev)
-            for names, x, *_ in batches:
-                idx = net.index_quantize(x)[0]
-                rec = net.decode_samples([idx])
-                for n, i_, r_ in zip(names, idx.cpu().numpy(), rec.float().cpu().numpy()):
-                    save_npy(i_, cfg["outputs_directory"], n, "quantization_0", np.uint16)
-                    save_npy(r_[0], cfg["outputs_directory"], n, "reconstruction", np.float32)
-        else:  # decoding: .npy uint16 code grids -> reconstructions (prepare_decoding_batch: .long())
-            files = list_inputs(cfg["training_subjects"], postfix="sample")[rank::world]
-            for f in files:
-                codes = np.load(f).astype(np.int64)
-                if codes.min() < 0 or codes.max() >= net.n_embed:   # e.g. a sampled BOS id (== vocab_size): torch's embedding lookup raises upstream too
-                    raise ValueError(f"{f}: code {int(codes.max())} is not a codebook entry (num_embeddings={net.n_embed})")
-                idx = torch.from_numpy(codes)[None].to(dev)
-                rec = net.decode_samples([idx])
-                save_npy(rec[0, 0].float().cpu().numpy(), cfg["outputs_directory"], f, "sample", np.float32)
+    saver = None
+    if cfg["output_ext"] != ".npy":      # volumes leave through sa_volume_egress and writer threads; the codes stay uint16 .npy
+        from synthanatomy_amd.utils.vqvae import NiftiSaver, nifti_output_geometry
+        saver = NiftiSaver(cfg["output_ext"], cfg["output_dtype"], min(int(cfg.get("num_workers") or 0), 8))
+        canonical = bool(cfg.get("load_nii_canonical", True))
+    try:
+        with torch.no_grad():
+            if cfg["mode"] == "extracting":
+                order = shard_for_rank(len(files), rank, world, shuffle=False, pad=False)   # even_divisible=False: no duplicates, no collectives
+                n_aug = int(cfg["no_augmented_extractions"] or 0)
+                if n_aug > 0:      # every subject n_aug times, augmentation_id i drawn as "epoch" i (reference src/utils/vqvae.py:126-181,194-196)
+                    batches = _augmented_batches([(_augmented_name(files[k], i), files[k], i, k) for k in order for i in range(n_aug)], cfg["eval_batch_size"],
+                                                 cfg, dev, "extracting", lambda k: _noise_seed(cfg["seed"], k * world + rank, 2))
+                else:
+                    batches = _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev)
+                for names, x, *headers in batches:
+                    idx = net.index_quantize(x)[0]
+                    rec = net.decode_samples([idx])
+                    if saver is None:
+                        for n, i_, r_ in zip(names, idx.cpu().numpy(), rec.float().cpu().numpy()):
+                            save_npy(i_, cfg["outputs_directory"], n, "quantization_0", np.uint16)
+                            save_npy(r_[0], cfg["outputs_directory"], n, "reconstruction", np.float32)
+                    else:          # straight from the decoder's output tensor, in the source file's own axes; the writers work while the next batch runs
+                        saver.batch()
+                        for n, r_, h in zip(names, rec, headers[0]):
+                            saver.save(r_[0], _output_path(cfg, n, "reconstruction"), *nifti_output_geometry(h, cfg["roi"], canonical, r_.shape[-3:]))
+                        for n, i_ in zip(names, idx.cpu().numpy()):
+                            save_npy(i_, cfg["outputs_directory"], n, "quantization_0", np.uint16)
+            else:  # decoding: .npy uint16 code grids -> reconstructions (prepare_decoding_batch: .long())
+                files = list_inputs(cfg["training_subjects"], postfix="sample")[rank::world]
+                group = max(min(int(cfg.get("num_workers") or 0), 8), 1)      # decoded volumes per batch of the saver: one per writer thread
+                for k, f in enumerate(files):
+                    codes = np.load(f).astype(np.int64)
+                    if codes.min() < 0 or codes.max() >= net.n_embed:   # e.g. a sampled BOS id (== vocab_size): torch's embedding lookup raises upstream too
+                        raise ValueError(f"{f}: code {int(codes.max())} is not a codebook entry (num_embeddings={net.n_embed})")
+                    idx = torch.from_numpy(codes)[None].to(dev)
+                    rec = net.decode_samples([idx])
+                    if saver is None:
+                        save_npy(rec[0, 0].float().cpu().numpy(), cfg["outputs_directory"], f, "sample", np.float32)
+                    else:          # no source metadata (upstream has none here either): the identity orientation and affine
+                        if k % group == 0:
+                            saver.batch()
+                        saver.save(rec[0, 0], _output_path(cfg, f, "sample"))
+    finally:
+        if saver is not None:      # every writer is joined (and its exception re-raised here) before "done"
+            saver.close()
     log(rank, f"{cfg['mode']} done: {len(files)} inputs -> {cfg['outputs_directory']}")
 
 
@@ -375,6 +433,7 @@ def run(argv):
     cfg = parse_flags(argv, DEFAULTS)
     if cfg["mode"] not in ("training", "extracting", "decoding"):
         raise ValueError(f"VQVAE mode unknown. Was given {cfg['mode']} but choices are ['training', 'extracting', 'decoding'].")
+    _check_output_flags(cfg)
     rank, local, world = init_distributed()
     cfg.update(rank=rank, local_rank=local, world_size=world)
     torch.manual_seed(cfg["seed"])

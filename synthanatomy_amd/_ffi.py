@@ -65,6 +65,12 @@ class IngestParams(Structure):
                 ("ext", c_int32 * 3), ("flags", c_int32), ("slope", ctypes.c_double), ("inter", ctypes.c_double)]
 
 
+class EgressParams(Structure):
+    """sa_egress_params (include/synthanatomy_hip.h): read on the host by sa_volume_egress."""
+    _fields_ = [("x_dtype", c_int32), ("dtype", c_int32), ("ext", c_int32 * 3), ("perm", c_int32 * 3), ("sign", c_int32 * 3), ("flags", c_int32),
+                ("slope", ctypes.c_double), ("inter", ctypes.c_double)]
+
+
 _SIGS = {
     "sa_abi_version": (c_int, []),
     "sa_last_error": (c_char_p, []),
@@ -114,6 +120,8 @@ _SIGS = {
     "sa_augment_workspace_bytes": (c_int64, [c_int]),
     "sa_volume_ingest": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sa_volume_ingest_workspace_bytes": (c_int64, []),
+    "sa_volume_egress": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sa_volume_egress_workspace_bytes": (c_int64, []),
     "sa_bn_sums_ws_floats": (c_int64, [c_int]),
     "sa_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "sa_embed_sum": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p]),

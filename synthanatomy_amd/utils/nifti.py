@@ -8,10 +8,15 @@ UNPINNED: nibabel and MONAI are not available offline.  The scaling rule, the af
 them on hand-built vectors whose answer does not depend on tie-breaking.
 
 Deliberate refusals: NIfTI-2, ``.hdr`` / ``.img`` pairs, complex / RGB / 64-bit integer / float128 voxels, more than three non-singleton dims, and
-canonical loading of a file without orientation (both codes 0: nothing is guessed)."""
+canonical loading of a file without orientation (both codes 0: nothing is guessed).
+
+The writer at the end of the file (``output_header``, ``output_affine``, ``write_nifti``) is the other direction on the same terms: standard
+library and numpy only, nibabel's ``Nifti1Image(data, affine)`` and MONAI's ``SegmentationSaver`` conventions restated and UNPINNED, the voxel block
+produced on the device by ``sa_volume_egress`` (csrc/egress.hip)."""
 from __future__ import annotations
 
 import gzip
+import os
 import struct
 from dataclasses import dataclass
 from typing import Optional
@@ -167,3 +172,73 @@ def header_orientation(header: NiftiHeader, canonical: bool) -> tuple:
 
 def is_nifti(path: str) -> bool:
     return isinstance(path, str) and path.endswith((".nii", ".nii.gz"))
+
+
+# ---- the writer: what SegmentationSaver(output_ext=".nii.gz", resample=False) -> nibabel.Nifti1Image(data, affine) leaves on disk, as far as
+# this package restates it.  UNPINNED like the reader: the header fields below are the restatement, ``parse_header`` reads back what is written, and the
+# voxel block comes from ``sa_volume_egress`` (csrc/egress.hip), not from numpy.
+
+def output_header(dims, datatype: int, affine, slope: float = 1.0, inter: float = 0.0) -> bytes:
+    """352 bytes: the little-endian NIfTI-1 header of a [n0, n1, n2] volume plus the four zero extension bytes, the voxel block follows at once
+    (vox_offset 352).  sform_code 2 with ``affine`` in srow_*, qform_code 0, pixdim[1..3] = the affine's column norms, xyzt_units 2 (mm).  float32 carries
+    scl_slope = scl_inter = 0 ("no scaling"); an integer datatype carries (slope, inter) as float32."""
+    if datatype not in (2, 4, 16):
+        raise ValueError(f"output_header: datatype = {datatype}: the writer stores uint8 (2), int16 (4) and float32 (16)")
+    dims = [int(n) for n in dims]
+    if len(dims) != 3 or any(not 1 <= n <= 32767 for n in dims):
+        raise ValueError(f"output_header: dims = {dims}: three extents in 1..32767")
+    aff = np.asarray(affine, dtype=np.float64)
+    if aff.shape != (4, 4) or not np.all(np.isfinite(aff)):
+        raise ValueError("output_header: the affine must be a finite 4 x 4 matrix")
+    h = bytearray(352)
+    struct.pack_into("<i", h, 0, 348)
+    struct.pack_into("<8h", h, 40, 3, *dims, 1, 1, 1, 1)
+    struct.pack_into("<2h", h, 70, datatype, 8 * DATATYPES[datatype][1])
+    zooms = np.sqrt((aff[:3, :3] ** 2).sum(axis=0))
+    struct.pack_into("<8f", h, 76, 1.0, *zooms, 1.0, 1.0, 1.0, 1.0)
+    struct.pack_into("<3f", h, 108, 352.0, *((0.0, 0.0) if datatype == 16 else (float(slope), float(inter))))
+    h[123] = 2
+    struct.pack_into("<2h", h, 252, 0, 2)
+    struct.pack_into("<12f", h, 280, *aff[:3].reshape(-1))
+    h[344:348] = b"n+1\0"
+    return bytes(h)
+
+
+def output_affine(src_affine, perm, sign, n_can, start, size) -> np.ndarray:
+    """The affine of the block [start, start + size) of a canonical volume, stored back in the SOURCE file's own axes: output voxel g is source-file
+    voxel g + s, with s = start[a] along file axis perm[a] where sign[a] > 0 and n_can[a] - start[a] - size[a] where the axis is reversed, so only the
+    translation changes: t' = R s + t.  (MONAI 0.5's crop leaves the affine untouched, so upstream's saved crop lands shifted: deliberately not
+    reproduced)  ``start`` may be negative (a file smaller than the ROI, mirror-padded).  ``src_affine`` None: the identity."""
+    if src_affine is None:
+        return np.eye(4)
+    aff = np.array(src_affine, dtype=np.float64)
+    s = np.zeros(3)
+    for a in range(3):
+        s[perm[a]] = start[a] if sign[a] > 0 else n_can[a] - start[a] - size[a]
+    aff[:3, 3] = aff[:3, :3] @ s + aff[:3, 3]
+    return aff
+
+
+def write_nifti(path, header_bytes: bytes, block) -> str:
+    """``header_bytes`` (``output_header``) and the voxel block (anything with the buffer protocol) -> ``path``: plain for ``.nii``, one gzip member for
+    ``.nii.gz`` (level 1: compression is the bound of this path; mtime 0 and no name: the bytes depend on the content only).  Written to ``<path>.part``
+    and renamed, so no reader ever sees a partial file under the final name."""
+    path = str(path)
+    if not is_nifti(path):
+        raise ValueError(f"write_nifti: {path}: the name must end in .nii or .nii.gz")
+    part = path + ".part"
+    try:
+        with open(part, "wb") as f:
+            if path.endswith(".gz"):
+                with gzip.GzipFile(filename="", mode="wb", compresslevel=1, fileobj=f, mtime=0) as z:
+                    z.write(header_bytes)
+                    z.write(block)
+            else:
+                f.write(header_bytes)
+                f.write(block)
+        os.replace(part, path)
+    except BaseException:
+        if os.path.exists(part):
+            os.remove(part)
+        raise
+    return path

@@ -2,6 +2,7 @@
 (``get_transformations``, reference ``src/utils/vqvae.py:183-371``) as per-sample parameter records for ``sa_augment`` (csrc/augment.hip)."""
 from __future__ import annotations
 
+import os
 from enum import Enum
 from math import floor
 
@@ -270,6 +271,138 @@ def hip_ingest(header, raw, window=None, normalize: bool = True, canonical: bool
     with torch.cuda.device(dev):
         _ffi.check(lib.sa_volume_ingest(_ffi.ptr(block), header.nbytes, _ffi.ptr(y), ctypes.byref(P), _ffi.ptr(ws), _ffi.stream()), "sa_volume_ingest")
     return (y, ws) if return_workspace else y
+
+
+EGRESS_AUTOSCALE = 1      # include/synthanatomy_hip.h: SA_EGRESS_AUTOSCALE
+EGRESS_DTYPES = {"float32": (16, 4), "int16": (4, 2), "uint8": (2, 1)}      # --output_dtype -> (NIfTI datatype code, bytes per voxel)
+_EGRESS_WS = {}           # device index -> zeroed workspace (sa_volume_egress resets it)
+
+
+def hip_egress(x, perm, sign, dtype: str = "float32", autoscale: bool = True, slope: float = 1.0, inter: float = 0.0, return_workspace: bool = False):
+    """``sa_volume_egress``: x [D, H, W] or [1, D, H, W], fp32 or bf16, contiguous, on the device, in canonical axes -> the NIfTI-1 voxel block as stored
+    (a uint8 device tensor; file dims n[perm[a]] = x.shape[a], axis 0 fastest, little-endian), the inverse of ``hip_ingest`` for the same (perm, sign).
+    Integer ``dtype``s also return (slope, inter) as the SECOND result: a device fp64 tensor [2] holding the pair the kernel used (``autoscale``: the pair
+    that covers the volume's finite range with the full code range; else the given one) -- read it after the stream has finished, e.g. behind the event
+    that guards the block's download.  One launch for float32, two with ``autoscale``, on the current stream.  ``return_workspace``: also the int64 view of
+    the workspace as the last result (word 2 = the float min | max << 32 of the finite voxels, word 3 = the number of non-finite voxels, stored as 0)."""
+    import ctypes
+
+    import torch
+    from .. import _ffi
+    if dtype not in EGRESS_DTYPES:
+        raise ValueError(f"hip_egress: dtype {dtype!r}: one of {sorted(EGRESS_DTYPES)}")
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1) or x.dtype not in (torch.float32, torch.bfloat16) \
+            or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"hip_egress: x must be a contiguous fp32 or bf16 tensor [D, H, W] or [1, D, H, W], got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__} {getattr(x, 'dtype', '')}")
+    perm, sign = [int(v) for v in perm], [int(v) for v in sign]
+    if sorted(perm) != [0, 1, 2] or len(sign) != 3 or any(s not in (1, -1) for s in sign):
+        raise ValueError(f"hip_egress: perm {perm} must be a permutation of (0, 1, 2) and sign {sign} three values of +1 / -1")
+    _ffi.require_gpu()
+    if not x.is_cuda:
+        raise ValueError("hip_egress: x must be a device tensor (there is no host path)")
+    ext = [int(v) for v in x.shape[-3:]]
+    code, size = EGRESS_DTYPES[dtype]
+    lib = _ffi.lib()
+    dev = x.device
+    ws = _EGRESS_WS.get(dev.index)
+    if ws is None:
+        ws = _EGRESS_WS[dev.index] = torch.zeros(8, dtype=torch.int64, device=dev)
+    assert lib.sa_volume_egress_workspace_bytes() <= ws.numel() * 8
+    P = _ffi.EgressParams(x_dtype=_ffi.dtype_id(x.dtype), dtype=code, flags=EGRESS_AUTOSCALE if autoscale and dtype != "float32" else 0, slope=float(slope),
+                          inter=float(inter))
+    P.ext[:], P.perm[:], P.sign[:] = ext, perm, sign
+    nbytes = ext[0] * ext[1] * ext[2] * size
+    raw = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(lib.sa_volume_egress(_ffi.ptr(x), _ffi.ptr(raw), nbytes, ctypes.byref(P), _ffi.ptr(ws), _ffi.stream()), "sa_volume_egress")
+    out = (raw,) if dtype == "float32" else (raw, ws[6:8].view(torch.float64).clone())
+    if return_workspace:
+        out += (ws,)
+    return out[0] if len(out) == 1 else out
+
+
+class NiftiSaver:
+    """NIfTI outputs of ``run_vqvae.py --output_ext=.nii|.nii.gz``: ``save`` turns a device volume into its voxel block with ``hip_egress``,
+    starts a non-blocking copy into a pinned host buffer and records an event; a writer thread (``workers`` of them; 0 = inline) waits for the event,
+    builds the header -- with the (slope, inter) the kernel used -- and writes the file (zlib and file I/O release the GIL), while the caller decodes the
+    next batch.  ``batch()`` opens a new batch (the caller decides what one is: an extraction batch, or as many decoded volumes as there are writers): at most two
+    batches of pinned buffers are in flight, a third waits for the oldest.  ``close()`` joins
+    every writer; a writer's exception is re-raised in the calling thread by ``batch()`` / ``close()``.  The bytes do not depend on ``workers``."""
+
+    def __init__(self, ext: str, dtype: str = "float32", workers: int = 0):
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        self.ext, self.dtype = ext, dtype
+        self.pool = ThreadPoolExecutor(workers) if workers > 0 else None
+        self.in_flight, self.current, self.free = deque(), [], {}
+
+    def _pinned(self, nbytes):
+        import torch
+        stack = self.free.setdefault(nbytes, [])
+        return stack.pop() if stack else torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+
+    def _write(self, event, host, pair, dims, affine, path):
+        from .nifti import output_header, write_nifti
+        event.synchronize()
+        slope, inter = (1.0, 0.0) if pair is None else pair.tolist()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        write_nifti(path, output_header(dims, EGRESS_DTYPES[self.dtype][0], affine, slope, inter), host.numpy())
+        self.free[host.numel()].append(host)
+        return path
+
+    def batch(self):
+        if self.current:
+            self.in_flight.append(self.current)
+            self.current = []
+        while len(self.in_flight) >= 2:
+            for f in self.in_flight.popleft():
+                f.result()
+
+    def save(self, x, path, perm=(0, 1, 2), sign=(1, 1, 1), affine=None):
+        """x [D, H, W] / [1, D, H, W] on the device in canonical axes -> ``path`` in the axes (perm, sign) describes, with ``affine`` (None: identity)."""
+        import torch
+        with torch.cuda.device(x.device):      # the copies and the event belong to the stream hip_egress launched on
+            out = hip_egress(x if x.is_contiguous() else x.contiguous(), perm, sign, self.dtype)
+            raw, pair = (out, None) if self.dtype == "float32" else out
+            host = self._pinned(raw.numel())
+            host.copy_(raw, non_blocking=True)
+            if pair is not None:
+                pair = torch.empty(2, dtype=torch.float64, pin_memory=True).copy_(pair, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        dims = [0, 0, 0]
+        for a in range(3):
+            dims[int(perm[a])] = int(x.shape[a - 3])
+        job = (event, host, pair, dims, np.eye(4) if affine is None else affine, path)
+        if self.pool is None:
+            self._write(*job)
+        else:
+            self.current.append(self.pool.submit(self._write, *job))
+
+    def close(self):
+        try:
+            self.batch()
+            while self.in_flight:
+                for f in self.in_flight.popleft():
+                    f.result()
+        finally:
+            if self.pool is not None:
+                self.pool.shutdown(wait=True)
+
+
+def nifti_output_geometry(header, roi, canonical: bool, size):
+    """(perm, sign, affine) of a NIfTI output of ``size`` (canonical axes) for a subject whose input was read from a NIfTI file with ``header`` (None: any
+    other input -- the identity orientation and affine): the file's own orientation with ``canonical`` (else the stored order), and
+    ``nifti.output_affine`` for the ROI window the loader cut (a file smaller than the ROI was mirror-padded: the window then starts before the file)."""
+    from .nifti import header_orientation, output_affine
+    if header is None:
+        return [0, 1, 2], [1, 1, 1], np.eye(4)
+    perm, sign = header_orientation(header, canonical)
+    n_can = [int(header.dims[k]) for k in perm]
+    start, cut = roi_window(roi, n_can) if roi else ([0, 0, 0], n_can)
+    start = [s - max(int(w) - c, 0) // 2 for s, c, w in zip(start, cut, size)]      # SpatialPadd puts (w - c) // 2 voxels in front
+    return perm, sign, output_affine(header.affine, perm, sign, n_can, start, [int(v) for v in size])
 
 
 def get_ms_ssim_window(config: dict, logger=None) -> int:

@@ -76,8 +76,10 @@ def _stage(script, argv, world, share_device):
     return round(time.perf_counter() - t0, 3)
 
 
-def run_chain(proj, exp="e2e_full", volumes=4, extract=4, samples=2, vq_batch=2, tr_batch=2, tr_epochs=2, world=1, share_device=False):
-    """Runs the five stages; returns {"seconds": {stage: s}, "codes": [...], "samples": [...], "decoded": [...], ...}."""
+def run_chain(proj, exp="e2e_full", volumes=4, extract=4, samples=2, vq_batch=2, tr_batch=2, tr_epochs=2, world=1, share_device=False, output_ext=".npy",
+              output_dtype="float32"):
+    """Runs the five stages; returns {"seconds": {stage: s}, "codes": [...], "samples": [...], "decoded": [...], ...}.  ``output_ext`` / ``output_dtype``: the
+    decode stage's --output_ext / --output_dtype (NIfTI samples)."""
     proj = proj if proj.endswith("/") else proj + "/"
     vq = vqvae_flags(proj, exp, vq_batch)
     tr = transformer_flags(proj, exp, tr_batch)
@@ -100,9 +102,9 @@ def run_chain(proj, exp="e2e_full", volumes=4, extract=4, samples=2, vq_batch=2,
         n_bos += int((s >= 2048).sum())
         if (s >= 2048).any():
             np.save(f, np.minimum(s, 2047).astype(np.uint16))
-    sec["vqvae_decoding"] = _stage("run_vqvae", vq + ["--training_subjects=" + out_tr, "--validation_subjects=synthetic:1", "--mode=decoding"],
-                                   world, share_device)
-    decoded = sorted(glob.glob(out_vq + "*/*_sample_sample.npy"))
+    sec["vqvae_decoding"] = _stage("run_vqvae", vq + ["--training_subjects=" + out_tr, "--validation_subjects=synthetic:1", "--mode=decoding",
+                                                      "--output_ext=" + output_ext, "--output_dtype=" + output_dtype], world, share_device)
+    decoded = sorted(glob.glob(out_vq + "*/*_sample_sample" + output_ext))
     return {"seconds": sec, "total_s": round(sum(sec.values()), 3), "world": world, "share_device": bool(share_device), "codes": codes,
             "samples": sampled, "decoded": decoded, "bos_tokens_clamped": n_bos, "project": proj, "experiment": exp,
             "workload": f"config-2 VQ-VAE (160x224x160, batch {vq_batch}) train 1 epoch of {volumes} -> extract {extract} -> Performer README widths "
@@ -115,7 +117,9 @@ if __name__ == "__main__":
     ap.add_argument("project")
     ap.add_argument("--world", type=int, default=1)
     ap.add_argument("--share-device", action="store_true")
+    ap.add_argument("--output_ext", default=".npy")
+    ap.add_argument("--output_dtype", default="float32")
     a = ap.parse_args()
-    res = run_chain(a.project, world=a.world, share_device=a.share_device)
+    res = run_chain(a.project, world=a.world, share_device=a.share_device, output_ext=a.output_ext, output_dtype=a.output_dtype)
     print(json.dumps({k: v for k, v in res.items() if k not in ("codes", "samples", "decoded")} | {"n_codes": len(res["codes"]),
                      "n_samples": len(res["samples"]), "n_decoded": len(res["decoded"])}))
