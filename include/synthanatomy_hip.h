@@ -99,7 +99,8 @@ int sa_kernel_log_read(char *buf, int cap, int stop);
 #define SA_DBG_RESERVED_20      (1u << 20)  /* (was SA_DBG_DENSE_RING: the four-wave ring GEMM of dense.hip -- slower on 7 of the 8 Performer shapes in round 5, removed in round 6) */
 #define SA_DBG_NO_CELLS256       (1u << 21)  /* stride-2 family on the im2col-order kernel instead of the 256-voxel cell mainloop (conv_fprop_cells256_kernel): A/B + cross-family tests */
 #define SA_DBG_NO_CLASS_LAUNCH    (1u << 22)  /* sa_conv_fprop_classes answers SA_EUNSUPPORTED: the parity classes of a transposed convolution as separate launches (A/B, equality test) */
-#define SA_DBG_FAVOR_SEQ_ALWAYS  (1u << 18)  /* FAVOR+ chunk states in the sequential form for every batch (default: from 40 (batch, head) pairs; tests) */
+#define SA_DBG_NO_STRIP_TILES     (1u << 23)  /* two-plane 3x3x3 halo tiles: the last 1..8 columns of a plane on ordinary 8 x 16 tiles instead of 16 x 8 strip tiles (A/B, equality test) */
+#define SA_DBG_FAVOR_SEQ_ALWAYS (1u << 18)  /* FAVOR+ chunk states in the sequential form for every batch (default: from 40 (batch, head) pairs; tests) */
 #define SA_DBG_DETERMINISTIC     (1u << 16)  /* fixed-order reductions where the library itself chooses (BatchNorm sums); see the deterministic-mode section */
 #define SA_DBG_SCAN_EXACT_SHIFT  10          /* 3 bits: chunk states | scan A outputs | scan B outputs on the exact-fp32 MFMA kernels */
 /* measurement aid (bench.py `roofline.peak_measured`): `blocks` x 4 waves each issue iters x 8 independent v_mfma_f32_32x32x16_bf16;

@@ -42,6 +42,8 @@ struct FpropArgs {
     const void* cls_wpk[8];
     uint32_t dbg;         // dev only (env SA_PP_DBG): 256 = LDS-staged epilogue instead of the register one; with -DSA_PP_DEBUG_VARIANTS also the
                           // ablation bits (halo: 1 skip halo DMA, 2 skip weight DMA, 64 skip epilogue; im2col-order: 64 / 128 skip activation / weight DMA)
+    uint32_t nblk_a, SB;  // two-plane halo mainloop with strip tiles: tiles [0, nblk_a) are ordinary ones on WP full column blocks, the rest 16 x 8 strip tiles in
+                          // SB bands of 16 rows on the columns from 16 WP on
 };
 
 template <typename T>

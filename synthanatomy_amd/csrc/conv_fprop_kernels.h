@@ -642,10 +642,18 @@ __device__ unsigned long long g_timing[8];
 // parity, so that consecutive kd groups -- visited innermost, (chunk, kd) order -- share one plane and a kd switch re-loads ONE plane (23 pieces) instead of the
 // whole image (41): 8 plane loads per tile instead of 6 images (180 vs 246 KB), half-size reload bubbles, and 8-row patches waste less at 40 x 56 x 40
 // (3 360 instead of 3 840 tiles).
-template <typename T, bool FUSE = false, int NW = 4, bool P2 = false>
+// STRIP (P2 only): tiles from a.nblk_a on are STRIP tiles of 2 x 16 (H) x 8 (W) voxels on the last Wo - 16 WP columns of the plane, where a 16-column tile would
+// compute eight columns or more that do not exist (Wo = 40: 2 880 instead of 3 360 tiles at 40 x 56 x 40, batch 8).  A strip tile's halo is 18 x 10 rows -- the
+// 180 rows of a plane slot again -- so LDS layout, piece count, swizzle, group / tap / K order and fragment layout are those of the ordinary tile; only the halo
+// row pitch (10) and the tile row <-> voxel map change (a 16-voxel fragment is 2 rows x 8 columns), and every output element sees the accumulation sequence it
+// sees in an ordinary tile: results are bit-identical.  Which kind a block works is block-uniform.  Without STRIP the kernel is the code it was.
+// (Measured: a strip fragment's rows r .. r+7 and r+10 .. r+17 are NOT conflict-free under the swizzle the way 16 consecutive rows are -- ~0.1 of a 40 x 56 x 40
+// launch's LDS cycles -- so a launch takes 0.87-0.90 of the time, not the 0.857 of the tile count.  DESIGN.md section 8 item 3.)
+template <typename T, bool FUSE = false, int NW = 4, bool P2 = false, bool STRIP = false>
 __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(const FpropArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(NW == 4 || NW == 8, "4 or 8 waves");
+    static_assert(!STRIP || P2, "strip tiles: two-plane tiles only");
     constexpr int MI = 32 / NW, NI = 4;
     constexpr int WPIECES = 16 / NW;          // weight pieces (1 KiB) per wave per slab
     constexpr int BN = 128;
@@ -667,14 +675,28 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
     const sa_conv_geom& g = a.g;
     // tile order = (n, band of 2 patch rows, d (P2: plane pair), row in band, wp)
     const uint32_t ND = P2 ? a.DP : (uint32_t)g.Dm;
-    const uint32_t per_vol = a.HP * a.WP * ND, band = 2u * a.WP * ND;
-    const uint32_t pn = bm / per_vol, rv = bm - pn * per_vol;
-    const uint32_t bc = rv / band, r2 = rv - bc * band;
-    const uint32_t rows_c = a.HP - 2u * bc < 2u ? a.HP - 2u * bc : 2u;
-    const uint32_t pd = r2 / (rows_c * a.WP), r3 = r2 - pd * rows_c * a.WP;
-    const uint32_t hpi = r3 / a.WP, wp = r3 - hpi * a.WP, hp = 2u * bc + hpi;
-    const int32_t h0 = (int32_t)hp * (P2 ? 8 : 16), w0 = (int32_t)wp * 16;
+    uint32_t pn, pd;
+    int32_t h0, w0;
+    const bool strip = STRIP && bm >= a.nblk_a;    // (block-uniform)
+    if (strip) {                                   // strip tiles, behind the ordinary ones: (n, band of 16 rows, plane pair)
+        const uint32_t sm = bm - a.nblk_a, per_vol_s = a.SB * a.DP;
+        pn = sm / per_vol_s;
+        const uint32_t rs = sm - pn * per_vol_s, sb = rs / a.DP;
+        pd = rs - sb * a.DP;
+        h0 = (int32_t)sb * 16, w0 = (int32_t)a.WP * 16;
+    } else {
+        const uint32_t per_vol = a.HP * a.WP * ND, band = 2u * a.WP * ND;
+        pn = bm / per_vol;
+        const uint32_t rv = bm - pn * per_vol;
+        const uint32_t bc = rv / band, r2 = rv - bc * band;
+        const uint32_t rows_c = a.HP - 2u * bc < 2u ? a.HP - 2u * bc : 2u;
+        pd = r2 / (rows_c * a.WP);
+        const uint32_t r3 = r2 - pd * rows_c * a.WP;
+        const uint32_t hpi = r3 / a.WP, wp = r3 - hpi * a.WP, hp = 2u * bc + hpi;
+        h0 = (int32_t)hp * (P2 ? 8 : 16), w0 = (int32_t)wp * 16;
+    }
     const int32_t d0 = P2 ? (int32_t)pd * 2 : (int32_t)pd;     // first output plane of the tile
+    const uint32_t hw = strip ? 10u : (uint32_t)HW_;           // halo rows per patch row: the row pitch of the halo image
     const int32_t oh = g.in_off[1] + (g.tap_step[1] < 0 ? 2 * g.tap_step[1] : 0), ow = g.in_off[2] + (g.tap_step[2] < 0 ? 2 * g.tap_step[2] : 0);
 
     __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, (int)a.in_bytes, 0x00020000);
@@ -703,7 +725,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
 #pragma unroll 1
         for (uint32_t p = wave; p < npieces; p += NW) {
             const uint32_t r = p * 8 + prow;
-            const uint32_t hh = r / HW_, ww = r - hh * HW_;
+            const uint32_t hh = strip ? r / 10u : r / HW_, ww = r - hh * hw;
             const int32_t ih = h0 + oh + (int32_t)hh, iw = w0 + ow + (int32_t)ww;
             const bool ok = dok && r < (uint32_t)HROWS && (uint32_t)ih < (uint32_t)g.Hi && (uint32_t)iw < (uint32_t)g.Wi;
             const uint32_t voff = ok ? (base_vox + (uint32_t)(ih * g.Wi + iw)) * vox_bytes + goff : OOB_OFF;
@@ -753,7 +775,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
 #endif
     const uint32_t frow = lane & 15u, fq = lane >> 4;
     // unswizzled; patch row j adds 18 * 128 j.  P2: the wave's rows are rows (wm & 1) * 4 .. of tile plane wm >> 1, whose slot depends on the group
-    const uint32_t a_base = P2 ? (((wm & 1u) * (uint32_t)MI) * HW_ + frow) * 128u + fq * 16u : ((wm * (uint32_t)MI) * HW_ + frow) * 128u + fq * 16u;
+    // strip tile: a fragment is 2 rows x 8 columns, the wave's rows are rows (wm & 1) * 8 .. and patch row j adds 20 * 128 j
+    const uint32_t a_base = strip ? (((wm & 1u) * 8u + (frow >> 3)) * 10u + (frow & 7u)) * 128u + fq * 16u
+                          : P2 ? (((wm & 1u) * (uint32_t)MI) * HW_ + frow) * 128u + fq * 16u : ((wm * (uint32_t)MI) * HW_ + frow) * 128u + fq * 16u;
+    const uint32_t a_step = strip ? 20u * 128u : HW_ * 128u;
     const uint32_t b_off = tile_off(wn * (NI * 16) + frow, fq);
     const bool fh = g.tap_step[1] < 0, fw = g.tap_step[2] < 0;
 
@@ -773,7 +798,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
 #pragma unroll 1
         for (uint32_t t9 = 0; t9 < 9; ++t9) {
             const uint32_t th = t9 / 3u, tw = t9 - th * 3u;
-            const uint32_t tapoff = ((fh ? 2u - th : th) * (uint32_t)HW_ + (fw ? 2u - tw : tw)) * 128u;
+            const uint32_t tapoff = ((fh ? 2u - th : th) * hw + (fw ? 2u - tw : tw)) * 128u;
             const unsigned char* pb = sB + buf * (BN * 128);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -786,7 +811,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
                 for (int i = 0; i < NI; ++i) wf[i] = *(const u32x4*)(pb + ((b_off + i * 2048u) ^ (ks * 64u)));
 #pragma unroll
                 for (int j = 0; j < MI; ++j) {
-                    const uint32_t ad = a_grp + tapoff + (uint32_t)j * (HW_ * 128u);
+                    const uint32_t ad = a_grp + tapoff + (uint32_t)j * a_step;
                     xf[j] = *(const u32x4*)(sA + ((ad ^ (((ad >> 7) & 7u) << 4)) ^ (ks * 64u)));
                 }
 #ifdef SA_MFMA32_PROBE
@@ -835,8 +860,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
     SA_TACC(0, s_comp); SA_TACC(1, s_dma); SA_TACC(2, s_bar); SA_TACC(3, s_halo);
 #endif
     auto row_vox = [&](uint32_t row) __attribute__((always_inline)) {
-        const uint32_t pr = row >> 4, w = (uint32_t)w0 + (row & 15u);
-        const uint32_t h = (uint32_t)h0 + (P2 ? (pr & 7u) : pr), d = (uint32_t)d0 + (P2 ? (pr >> 3) : 0u);
+        const uint32_t pr = row >> 4, w = (uint32_t)w0 + (strip ? row & 7u : row & 15u);
+        const uint32_t h = (uint32_t)h0 + (strip ? (pr & 7u) * 2u + ((row >> 3) & 1u) : P2 ? (pr & 7u) : pr), d = (uint32_t)d0 + (P2 ? (pr >> 3) : 0u);
         return d < (uint32_t)g.Do && h < (uint32_t)g.Ho && w < (uint32_t)g.Wo ? (((long long)pn * g.Do + d) * g.Ho + h) * g.Wo + w : -1ll;
     };
 #ifdef SA_MFMA32_PROBE
@@ -1212,11 +1237,11 @@ static bool halo256_eligible(const FpropArgs& a, int sz) {
     return eff >= 0.7 && (int64_t)g.N * g.Dm * hp * wp >= 256;
 }
 
-template <typename T, bool FUSE, int NW, bool P2 = false>
+template <typename T, bool FUSE, int NW, bool P2 = false, bool STRIP = false>
 static int launch_fprop_halo256_impl(const FpropArgs& a, uint32_t nbn, size_t lds, hipStream_t st) {
     static std::atomic<uint64_t> attr_done{0};   // one bit per device (one static per template instance)
-    configure_once_per_device(attr_done, [] { (void)hipFuncSetAttribute((const void*)conv_fprop_halo256_kernel<T, FUSE, NW, P2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); });
-    hipLaunchKernelGGL((conv_fprop_halo256_kernel<T, FUSE, NW, P2>), dim3(a.nblk_m * nbn), dim3(NW * 64), lds, st, a);
+    configure_once_per_device(attr_done, [] { (void)hipFuncSetAttribute((const void*)conv_fprop_halo256_kernel<T, FUSE, NW, P2, STRIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); });
+    hipLaunchKernelGGL((conv_fprop_halo256_kernel<T, FUSE, NW, P2, STRIP>), dim3(a.nblk_m * nbn), dim3(NW * 64), lds, st, a);
     SA_CHECK_LAUNCH();
     return 0;
 }
@@ -1230,12 +1255,27 @@ static int launch_fprop_halo256(FpropArgs a, hipStream_t st) {
         const int hp8 = (a.g.Ho + 7) / 8, hp16 = (a.g.Ho + 15) / 16, wp = (a.g.Wo + 15) / 16, dp = (a.g.Dm + 1) / 2;
         const int64_t tiles1 = (int64_t)a.g.Dm * hp16 * wp, tiles2 = (int64_t)dp * hp8 * wp;
         const bool p2 = !(g_tunables.pp_dbg & 1024u) && ((g_tunables.pp_dbg & 4096u) ? true : tiles2 <= tiles1);
+        const size_t lds = 46 * 1024 + 2 * 128 * 128;   // 78 KiB: two plane slots + two weight slabs (>= the 64 KiB hidden tile of the fused variant)
+        // strip tiles: with two-plane tiles chosen, the last 1 .. 8 columns behind wa full 16-column blocks go to 16 (H) x 8 (W) tiles when that takes fewer tiles
+        // (40 x 56 x 40: 6 x (7 x 2 + 4) = 108 per volume instead of 6 x 21 = 126).  Same K order, bit-identical results; SA_DBG_NO_STRIP_TILES restores the plan
+        // without them.
+        const int wa = a.g.Wo / 16, rem = a.g.Wo - 16 * wa;
+        const int64_t tiles3 = (int64_t)dp * (hp8 * wa + hp16);
+        if (p2 && wa >= 1 && rem >= 1 && rem <= 8 && tiles3 < tiles2 && tiles3 <= tiles1 && !dbg(SA_DBG_NO_STRIP_TILES)) {
+            a.HP = (uint32_t)hp8;
+            a.WP = (uint32_t)wa;
+            a.DP = (uint32_t)dp;
+            a.SB = (uint32_t)hp16;
+            a.nblk_a = (uint32_t)a.g.N * a.DP * a.HP * a.WP;
+            a.nblk_m = a.nblk_a + (uint32_t)a.g.N * a.DP * a.SB;
+            (snprintf(g_last_conv_kernel, sizeof g_last_conv_kernel, "conv_fprop_halo256_kernel<%s, %s, 8, true, true>", tname<T>(), FUSE ? "true" : "false"), note_kernel(g_last_conv_kernel));
+            return launch_fprop_halo256_impl<T, FUSE, 8, true, true>(a, nbn, lds, st);
+        }
         if (p2) {
             a.HP = (uint32_t)hp8;
             a.WP = (uint32_t)wp;
             a.DP = (uint32_t)dp;
             a.nblk_m = (uint32_t)a.g.N * a.DP * a.HP * a.WP;
-            const size_t lds = 46 * 1024 + 2 * 128 * 128;   // 78 KiB: two plane slots + two weight slabs (>= the 64 KiB hidden tile of the fused variant)
             (snprintf(g_last_conv_kernel, sizeof g_last_conv_kernel, "conv_fprop_halo256_kernel<%s, %s, 8, true>", tname<T>(), FUSE ? "true" : "false"), note_kernel(g_last_conv_kernel));
             return launch_fprop_halo256_impl<T, FUSE, 8, true>(a, nbn, lds, st);
         }
