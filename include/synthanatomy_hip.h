@@ -541,6 +541,24 @@ int sa_convt1_bwd(const void *x, int dtype, const float *w, const float *g, cons
 int sa_convt1_gather(const float *p, const float *bias, float *out, int N, int D, int H, int W, void *stream);
 int sa_convt1_im2col(const float *g, int dtype, void *gc, float *db, int N, int D, int H, int W, void *stream);
 
+/* ---- the one-channel ends for every other sampling geometry (csrc/taps.hip): nn.Conv3d(1 -> C) / nn.ConvTranspose3d(C -> 1) with kernel k = 1 .. 4,
+ * stride 1 or 2, any padding / dilation / output_padding (baseline.py:218-226, :283-293 with the CLI's --downsample_parameters / --upsample_parameters).
+ * The k^3 taps, t = (td * k + th) * k + tw, are the channels of a 1x1x1 convolution over cells (sa_conv_fprop / sa_conv_wgrad); rows hold `ld` >= k^3
+ * elements, a multiple of 16 bytes.
+ * sa_taps_unfold: xc[n][m][t] = x[n][m * mult + t * step + off] per axis, zero outside the fp32 volume x [N, Di, Hi, Wi], for the cells m of the grid
+ *                 (Dm, Hm, Wm) the caller names; stored as `dtype` (SA_F32 / SA_BF16 / SA_F16, round to nearest even; finite values beyond the half range
+ *                 saturate like every f16 store of this library), columns k^3 .. ld - 1 zeroed; db (may be NULL) += the sum of x.
+ *                 First layer forward: mult = stride, step = dilation, off = -padding.  Last layer backward: the same numbers, x = the output gradient.
+ * sa_taps_fold  : out[n][o] = bias[0] + sum of p[n][(o + pad - t * dil) / stride][t] over the taps t whose quotient is an integer inside the cell grid
+ *                 (Dc, Hc, Wc) on every axis; p fp32 [N, Dc, Hc, Wc, ld], out fp32 [N, Do, Ho, Wo] of any size (output_padding included).  One thread per
+ *                 output voxel, taps in the order of t: no atomics, bitwise reproducible.
+ * SA_EINVAL: NULL x / xc / p / out, ld < k^3 or not a multiple of 16 bytes, non-positive extents, element counts or coordinates >= 2^31 - 16;
+ * SA_EUNSUPPORTED: k outside 1 .. 4, stride outside 1 .. 2, another dtype. */
+int sa_taps_unfold(const float *x, int dtype, void *xc, float *db, int N, int Di, int Hi, int Wi, int Dm, int Hm, int Wm, int k, int mult, int step, int off,
+                   int ld, void *stream);
+int sa_taps_fold(const float *p, const float *bias, float *out, int N, int Dc, int Hc, int Wc, int Do, int Ho, int Wo, int k, int stride, int pad, int dil,
+                 int ld, void *stream);
+
 /* ---- FAVOR+ global heads with the feature maps recomputed on chip (csrc/favor_fused.hip; throughput mode) ------------------------------------
  * Replaces, for performer_pytorch.FastAttention / softmax_kernel / causal_linear_attention (reference src/networks/transformers/performer.py:194-219
  * delegates to them), the chain sa_favor_project* -> sa_favor_features_fwd -> sa_favor_scan_a_norm (forward) and sa_favor_dden -> sa_favor_scan_b_cum x2 ->

@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _ffi, debug
+from . import _ffi, conv_plan, debug
 from ._ffi import ACT_NONE, MASK_NONE, ConvGeom, Epilogue
 
 
@@ -115,30 +115,23 @@ def make_geom(dtype, N, grid, idims, cin_s, odims, cout_s, cin_valid, cout_valid
     return g
 
 
-def _parities():
-    return [(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)]
-
-
-def _parity_lut(par, k=4):
-    k0 = [(p + 1) % 2 for p in par]
-    return [((k0[0] + 2 * td) * k + (k0[1] + 2 * th)) * k + (k0[2] + 2 * tw) for td in (0, 1) for th in (0, 1) for tw in (0, 1)]
-
-
 class ConvOp:
-    """kind="conv": weight [Cout, Cin, k,k,k];  kind="convT": weight [Cin, Cout, k,k,k] (k4 s2 p1 only)."""
+    """kind="conv": weight [Cout, Cin, k,k,k];  kind="convT": weight [Cin, Cout, k,k,k].  Any (k, stride, pad, output_pad, dilation) the planner
+    takes (conv_plan.check_tuple: kernel 1 .. 4, stride 1 or 2, every residue class of the stride owning a tap)."""
 
     def __init__(self, kind: str, cin: int, cout: int, k: int, stride: int, pad: int, weight: torch.Tensor, bias: Optional[torch.Tensor],
-                 dtype: torch.dtype, w_strides: Optional[Tuple[int, int]] = None, fwd_dtype: Optional[torch.dtype] = None):
+                 dtype: torch.dtype, w_strides: Optional[Tuple[int, int]] = None, fwd_dtype: Optional[torch.dtype] = None, output_pad: int = 0,
+                 dilation: int = 1):
         """`w_strides` = (stride of cout, stride of cin) in elements of `weight` for a 1x1x1 "conv" whose weight is stored transposed
-        (the 64 taps of the final ConvTranspose3d as output channels): forward and wgrad only.
+        (the taps of the final ConvTranspose3d as output channels): forward and wgrad only.
         `fwd_dtype` (torch.float16 with dtype = torch.bfloat16): the FORWARD launches take f16 activations and an f16-packed operand and write f16
         (+ a bf16 copy on request, `want_lp`); data and weight gradients stay in `dtype` -- the reference's AMP forward (src/engines/trainer.py:161-163)."""
         assert kind in ("conv", "convT")
         assert w_strides is None or (kind == "conv" and k == 1)
         self.w_strides = w_strides
-        if kind == "convT" and not (k == 4 and stride == 2 and pad == 1):
-            raise NotImplementedError("ConvTranspose3d is implemented for kernel 4 / stride 2 / padding 1 / output_padding 0 (the reference's setting)")
+        conv_plan.check_tuple(kind, k, stride, pad, output_pad, dilation)
         self.kind, self.cin, self.cout, self.k, self.stride, self.pad = kind, cin, cout, k, stride, pad
+        self.output_pad, self.dilation = output_pad, dilation
         self.weight, self.bias = weight, bias
         self.dtype = dtype
         self.fwd_dtype = fwd_dtype or dtype
@@ -152,53 +145,39 @@ class ConvOp:
 
     # ------------------------------------------------------------------ shapes
     def out_dims(self, idims):
-        if self.kind == "conv":
-            return tuple((d + 2 * self.pad - self.k) // self.stride + 1 for d in idims)
-        return tuple(2 * d for d in idims)
+        return tuple(conv_plan.out_size(self.kind, self.k, self.stride, self.pad, self.output_pad, self.dilation, d) for d in idims)
 
     def cs_in(self):
         return _ru(self.cin, self.vec)
 
     # ------------------------------------------------------------------ plans
     def _get_plans(self, N: int, idims: Tuple[int, int, int], cout_s: int, gout_s: int):
+        """One _Plan per class of conv_plan.plan.  Forward and weight-gradient launches read the input [.., cin_s] and are laid over the output; data-gradient
+        launches read the output gradient [.., gout_s] and are laid over the input, with the channel roles (and the weight strides) swapped."""
         key = (N, tuple(idims), cout_s, gout_s)
         if key in self._plans:
             return self._plans[key]
-        dt, k, s, p, T = self.dtype, self.k, self.stride, self.pad, self.T
+        dt, T = self.dtype, self.T
         cin, cout = self.cin, self.cout
         cin_s = self.cs_in()
-        odims = self.out_dims(idims)
-        fwd: List[_Plan] = []
-        dgr: List[_Plan] = []
-        wgr: List[_Plan] = []
-        one, zero = (1, 1, 1), (0, 0, 0)
+        cp = conv_plan.plan(self.kind, self.k, self.stride, self.pad, self.output_pad, self.dilation, idims)
+        odims = cp["odims"]
         if self.kind == "conv":
             sr, sd = self.w_strides if self.w_strides is not None else (cin * T, T)
-            g = make_geom(dt, N, odims, idims, cin_s, odims, cout_s, cin, cout, (k,) * 3, (s,) * 3, one, (-p,) * 3, one, zero)
-            fwd.append(_Plan(g, cout, cin, T, None, sr, sd))
-            gw = make_geom(dt, N, odims, idims, cin_s, odims, gout_s, cin, cout, (k,) * 3, (s,) * 3, one, (-p,) * 3, one, zero)
-            wgr.append(_Plan(gw, cout, cin, T, None, sr, sd))
-            if self.w_strides is not None:
-                dgr = None
-            elif s == 1:
-                g = make_geom(dt, N, idims, odims, gout_s, idims, cin_s, cout, cin, (k,) * 3, one, (-1,) * 3, (p,) * 3, one, zero)
-                dgr.append(_Plan(g, cin, cout, T, None, T, cin * T))
-            elif s == 2 and k == 4 and p == 1 and all(d % 2 == 0 for d in idims):
-                half = tuple(d // 2 for d in idims)
-                for par in _parities():
-                    g = make_geom(dt, N, half, odims, gout_s, idims, cin_s, cout, cin, (2, 2, 2), one, (-1,) * 3, par, (2, 2, 2), par)
-                    dgr.append(_Plan(g, cin, cout, 8, _parity_lut(par), T, cin * T))
-            else:
-                dgr = None  # data gradient not available for this geometry
-        else:  # convT k4 s2 p1
-            for par in _parities():
-                lut = _parity_lut(par)
-                g = make_geom(dt, N, idims, idims, cin_s, odims, cout_s, cin, cout, (2, 2, 2), one, (-1,) * 3, par, (2, 2, 2), par)
-                fwd.append(_Plan(g, cout, cin, 8, lut, T, cout * T))
-                gw = make_geom(dt, N, idims, idims, cin_s, odims, gout_s, cin, cout, (2, 2, 2), one, (-1,) * 3, par, (2, 2, 2), par)
-                wgr.append(_Plan(gw, cout, cin, 8, lut, T, cout * T))
-            g = make_geom(dt, N, idims, odims, gout_s, idims, cin_s, cout, cin, (4,) * 3, (2, 2, 2), one, (-1,) * 3, one, zero)
-            dgr.append(_Plan(g, cin, cout, T, None, cout * T, T))
+        else:
+            sr, sd = T, cout * T
+
+        def geom(c, out_s, transposed):
+            if transposed:   # data gradient: gradient in, dx out
+                return make_geom(dt, N, c["grid"], odims, gout_s, idims, cin_s, cout, cin, c["KT"], c["in_mult"], c["tap_step"], c["in_off"], c["out_mult"], c["out_off"])
+            return make_geom(dt, N, c["grid"], idims, cin_s, odims, out_s, cin, cout, c["KT"], c["in_mult"], c["tap_step"], c["in_off"], c["out_mult"], c["out_off"])
+
+        def ntaps(c):
+            return c["KT"][0] * c["KT"][1] * c["KT"][2]
+
+        fwd = [_Plan(geom(c, cout_s, False), cout, cin, ntaps(c), c["lut"], sr, sd) for c in cp["fwd"]]
+        wgr = [_Plan(geom(c, gout_s, False), cout, cin, ntaps(c), c["lut"], sr, sd) for c in cp["wgrad"]]
+        dgr = None if self.w_strides is not None else [_Plan(geom(c, None, True), cin, cout, ntaps(c), c["lut"], sd, sr) for c in cp["dgrad"]]
         plans = {"fwd": fwd, "dgrad": dgr, "wgrad": wgr, "odims": odims}
         if len(self._plans) > 64:  # autoregressive sampling visits every prefix length once: keep the cache bounded
             self._plans.pop(next(iter(self._plans)))
@@ -332,7 +311,7 @@ class ConvOp:
         assert g.dtype == self.dtype and g.is_contiguous() and gout_s >= self.cout and gout_s % self.vec == 0
         plans = self._get_plans(N, tuple(idims), fwd_out_stride or self.cout, gout_s)
         if plans["dgrad"] is None:
-            raise NotImplementedError("data gradient for this conv geometry")
+            raise NotImplementedError("data gradient of a 1x1x1 convolution whose weight is stored transposed (w_strides)")
         self._ensure_packed(plans["dgrad"])
         out_dtype = out_dtype or self.dtype
         cin_s = self.cs_in()

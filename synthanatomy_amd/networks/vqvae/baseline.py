@@ -21,9 +21,9 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ... import _ffi, debug
+from ... import _ffi, conv_plan, debug
 from ..._ffi import ACT_NONE, ACT_RELU, MASK_NONE, MASK_POS
-from ...engine import ConvOp, PackSet, _launch, _ru, cast_pad, vec_of
+from ...engine import ConvOp, PackSet, _launch, _ru, _tbytes, cast_pad, vec_of
 from .vqvae import VQVAEBase
 
 
@@ -224,14 +224,50 @@ def _fs(x):
     return (x.f, x.s) if isinstance(x, _Act) else (x, x)
 
 
+def _module_tuple(mod):
+    """(kernel, stride, padding, output_padding, dilation) of an isotropic nn.Conv3d / nn.ConvTranspose3d"""
+    for v in (mod.kernel_size, mod.stride, mod.padding, mod.dilation, getattr(mod, "output_padding", (0, 0, 0))):
+        if len(set(v)) != 1:
+            raise NotImplementedError(f"anisotropic convolution parameters {tuple(v)}")
+    return mod.kernel_size[0], mod.stride[0], mod.padding[0], (mod.output_padding[0] if isinstance(mod, nn.ConvTranspose3d) else 0), mod.dilation[0]
+
+
+def _tuple_supported(kind, mod) -> bool:
+    try:
+        k, s, p, op, d = _module_tuple(mod)
+        conv_plan.check_tuple(kind, k, s, p, op, d)
+    except (NotImplementedError, ValueError):
+        return False
+    return True
+
+
+def taps_unfold(x, dtype, grid, k, mult, step, off, ld, db=None):
+    """Xc [N, *grid, ld] (`dtype`) from the fp32 volume x [N, D, H, W] (sa_taps_unfold, csrc/taps.hip); db += sum x."""
+    N, D, H, W = x.shape
+    Xc = torch.empty((N, *grid, ld), dtype=dtype, device=x.device)
+    _launch("taps_unfold_kernel", 0.0, nbytes=_tbytes(x, Xc),
+            fn=lambda: _ffi.check(_ffi.lib().sa_taps_unfold(_ffi.ptr(x), _ffi.dtype_id(dtype), _ffi.ptr(Xc), _ffi.ptr(db), N, D, H, W, *grid, k, mult, step, off, ld,
+                                                            _ffi.stream()), "sa_taps_unfold"))
+    return Xc
+
+
+def taps_fold(P, bias, odims, k, s, p, d):
+    """out [N, *odims] fp32 from P [N, D, H, W, ld] fp32 (sa_taps_fold, csrc/taps.hip)."""
+    N, D, H, W, ld = P.shape
+    out = torch.empty((N, *odims), dtype=torch.float32, device=P.device)
+    _launch("taps_fold_kernel", 0.0, nbytes=_tbytes(P, out),
+            fn=lambda: _ffi.check(_ffi.lib().sa_taps_fold(_ffi.ptr(P), _ffi.ptr(bias), _ffi.ptr(out), N, D, H, W, *odims, k, s, p, d, ld, _ffi.stream()), "sa_taps_fold"))
+    return out
+
+
 class _ConvStage:
     """conv / convT (+ReLU).  ``in_act``: the stage's input is a post-ReLU tensor, so the data gradient it hands back is
     masked with (x > 0) in the dgrad epilogue."""
 
     def __init__(self, mod: nn.Module, kind, act, in_act, dtype, out_f32=False, need_dx=True, fwd_dtype=None):
-        k, s, p = mod.kernel_size[0], mod.stride[0], mod.padding[0]
+        k, s, p, op, d = _module_tuple(mod)
         self.mod, self.act, self.in_act, self.out_f32, self.need_dx = mod, act, in_act, out_f32, need_dx
-        self.op = ConvOp(kind, mod.in_channels, mod.out_channels, k, s, p, mod.weight, mod.bias, dtype, fwd_dtype=fwd_dtype)
+        self.op = ConvOp(kind, mod.in_channels, mod.out_channels, k, s, p, mod.weight, mod.bias, dtype, fwd_dtype=fwd_dtype, output_pad=op, dilation=d)
         self.dtype = dtype
         self.mixed = self.op.fwd_dtype != dtype
 
@@ -275,38 +311,70 @@ class _Conv1Stage:
     runs the MFMA from there, forward (+bias, ReLU) and weight / bias gradient -- only the output / the incoming gradient touch HBM.
     Other widths / fp32: sa_convt1_im2col writes Xc[cell][tap] = x[2 cell - 1 + tap] (the gather the last decoder layer's backward uses)
     and the dense kernels treat the taps as the channels of a 1x1x1 convolution.  No data gradient: this is the network input.  Odd extents
-    or tiny volumes take the generic stage."""
+    or tiny volumes take the generic stage.
+    Every other (kernel, stride, padding, dilation) the planner takes: sa_taps_unfold (csrc/taps.hip) writes Xc[cell][tap] for the k^3 taps at any
+    extent, and the same dense launches follow; an f16 forward chain unfolds to f16 and the backward pass unfolds the volume again to bf16."""
 
     GEMM_MIN_CELLS = 4096
 
     def __init__(self, mod: nn.Conv3d, act, dtype, fwd_dtype=None):
         self.mod, self.act, self.dtype = mod, act, dtype
-        self.op = ConvOp("conv", 64, mod.out_channels, 1, 1, 0, mod.weight.view(mod.out_channels, 64, 1, 1, 1), mod.bias, dtype, fwd_dtype=fwd_dtype)
+        self.tuple = _module_tuple(mod)
+        self.default = self.tuple == (4, 2, 1, 0, 1)
+        self.T = self.tuple[0] ** 3
+        self.op = ConvOp("conv", self.T, mod.out_channels, 1, 1, 0, mod.weight.view(mod.out_channels, self.T, 1, 1, 1), mod.bias, dtype, fwd_dtype=fwd_dtype)
         self.mixed = self.op.fwd_dtype != dtype
         self.fallback = _ConvStage(mod, "conv", act, in_act=False, dtype=dtype, need_dx=False, fwd_dtype=fwd_dtype)
         self.fallback_op = self.fallback.op
 
     @staticmethod
     def applicable(mod) -> bool:
-        return (isinstance(mod, nn.Conv3d) and mod.in_channels == 1 and mod.kernel_size == (4, 4, 4) and mod.stride == (2, 2, 2)
-                and mod.padding == (1, 1, 1) and mod.dilation == (1, 1, 1) and mod.out_channels % 8 == 0)
+        return isinstance(mod, nn.Conv3d) and mod.in_channels == 1 and mod.out_channels % 8 == 0 and _tuple_supported("conv", mod)
 
     def params(self):
         return [self.mod.weight, self.mod.bias]
 
     def _sync(self):
-        self.op.weight, self.op.bias = self.mod.weight.view(self.mod.out_channels, 64, 1, 1, 1), self.mod.bias
+        self.op.weight, self.op.bias = self.mod.weight.view(self.mod.out_channels, self.T, 1, 1, 1), self.mod.bias
+
+    def _fwd_generic(self, x, tape):
+        vec = vec_of(self.dtype)
+        xc = cast_pad(x.unsqueeze(-1), self.op.fwd_dtype, vec)
+        return self.fallback.fwd(_Act(xc, cast_pad(x.unsqueeze(-1), self.dtype, vec) if tape is not None else None) if self.mixed else xc, tape)
+
+    def _unfold(self, x, dtype):
+        k, s, p, _, d = self.tuple
+        return taps_unfold(x, dtype, self.fallback_op.out_dims(tuple(x.shape[1:])), k, s, d, -p, self.op.cs_in())
+
+    def _fwd_taps(self, x, tape):
+        """any supported tuple, any extent: unfold + the dense launches over the k^3 taps"""
+        od = self.fallback_op.out_dims(tuple(x.shape[1:]))
+        if x.shape[0] * od[0] * od[1] * od[2] < self.GEMM_MIN_CELLS:
+            return self._fwd_generic(x, tape)
+        self._sync()
+        cout = self.op.cout
+        Xc = self._unfold(x, self.op.fwd_dtype)
+        if not self.mixed:
+            y = self.op.fprop(Xc, act=self.act, out_dtype=self.dtype, out_channels_stride=cout)
+            if tape is not None:
+                tape.append((Xc, "im2col"))
+            return y
+        if tape is None:
+            return _Act(self.op.fprop(Xc, act=self.act, out_channels_stride=cout), None)
+        y, _, ys = self.op.fprop(Xc, act=self.act, out_channels_stride=cout, want_lp=True)
+        tape.append((x, "unfold"))
+        return _Act(y, ys)
 
     def fwd(self, x, tape):
         """x: the raw fp32 volume [N, D, H, W]."""
+        if not self.default:
+            return self._fwd_taps(x, tape)
         N, D, H, W = x.shape
         Do, Ho, Wo, cout = D // 2, H // 2, W // 2, self.op.cout
         fused = (self.dtype == torch.bfloat16 and cout == 128 and not debug.deterministic())   # (its weight gradient ends in fp32 atomics)
         if (D % 2 or H % 2 or W % 2 or Wo < 2 or N * Do * Ho * Wo < self.GEMM_MIN_CELLS   # generic stage
                 or (self.mixed and not fused)):      # (an f16 forward chain has the fused kernel and the generic stage, not the im2col route)
-            vec = vec_of(self.dtype)
-            xc = cast_pad(x.unsqueeze(-1), self.op.fwd_dtype, vec)
-            return self.fallback.fwd(_Act(xc, cast_pad(x.unsqueeze(-1), self.dtype, vec) if tape is not None else None) if self.mixed else xc, tape)
+            return self._fwd_generic(x, tape)
         self._sync()
         lib, st = _ffi.lib(), _ffi.stream()
         if fused:
@@ -347,7 +415,8 @@ class _Conv1Stage:
                     lambda: _ffi.check(_ffi.lib().sa_conv1_wgrad(_ffi.ptr(x), _ffi.ptr(G), _ffi.ptr(dw), _ffi.ptr(db), N, D // 2, H // 2, W // 2, self.op.cout,
                                                                  _ffi.stream()), "sa_conv1_wgrad"))
         else:
-            self.op.wgrad(saved[0], G, dw.view(self.mod.out_channels, 64, 1, 1, 1), db)
+            Xc = self._unfold(saved[0], self.dtype) if saved[1] == "unfold" else saved[0]
+            self.op.wgrad(Xc, G, dw.view(self.mod.out_channels, self.T, 1, 1, 1), db)
         grads.done(self.mod.weight, self.mod.bias)
         return None
 
@@ -355,20 +424,32 @@ class _Conv1Stage:
 class _ConvT1Stage:
     """Final ConvTranspose3d(128 -> 1, k4 s2 p1) (csrc/convt1.hip).  At scale the 64 taps become the channels of a 1x1x1 convolution on
     the MFMA kernels (P = x . w per cell, then a gather onto the output grid; backward: im2col of the gradient, then the 1x1x1 dgrad /
-    wgrad); tiny inputs use the direct kernels."""
+    wgrad); tiny inputs use the direct kernels.
+    Every other (kernel, stride, padding, output_padding, dilation) the planner takes, at any width: the same two dense launches between sa_taps_fold /
+    sa_taps_unfold (csrc/taps.hip) over the k^3 taps; below GEMM_MIN_CELLS the generic stage."""
 
     GEMM_MIN_CELLS = 4096
 
     def __init__(self, mod: nn.ConvTranspose3d, in_act, dtype):
         self.mod, self.in_act, self.dtype = mod, in_act, dtype
-        # taps as output channels: weight[c][tap] read with (cout stride, cin stride) = (1, 64)
-        self.taps_fwd = ConvOp("conv", 128, 64, 1, 1, 0, mod.weight, None, dtype, w_strides=(1, 64))
-        self.taps_bwd = ConvOp("conv", 64, 128, 1, 1, 0, mod.weight, None, dtype)
+        self.tuple = _module_tuple(mod)
+        self.default = self.tuple == (4, 2, 1, 0, 1)
+        C, T = mod.in_channels, self.tuple[0] ** 3
+        self.T = T
+        # taps as output channels: weight[c][tap] read with (cout stride, cin stride) = (1, T)
+        self.taps_fwd = ConvOp("conv", C, T, 1, 1, 0, mod.weight, None, dtype, w_strides=(1, T))
+        self.taps_bwd = ConvOp("conv", T, C, 1, 1, 0, mod.weight, None, dtype)
+        if not self.default:
+            self.fallback = _ConvStage(mod, "convT", ACT_NONE, in_act=in_act, dtype=dtype, out_f32=True)
+            self.fallback_op = self.fallback.op
 
     @staticmethod
     def applicable(mod) -> bool:
-        return (isinstance(mod, nn.ConvTranspose3d) and mod.in_channels == 128 and mod.out_channels == 1 and mod.kernel_size == (4, 4, 4)
-                and mod.stride == (2, 2, 2) and mod.padding == (1, 1, 1))
+        if not (isinstance(mod, nn.ConvTranspose3d) and mod.out_channels == 1 and _tuple_supported("convT", mod)):
+            return False
+        if _module_tuple(mod) == (4, 2, 1, 0, 1):
+            return mod.in_channels == 128        # the specialised kernels of csrc/convt1.hip
+        return mod.in_channels % 8 == 0
 
     def params(self):
         return [self.mod.weight, self.mod.bias]
@@ -379,7 +460,42 @@ class _ConvT1Stage:
     def _gemm(self, x):
         return x.numel() // 128 >= self.GEMM_MIN_CELLS or debug.deterministic()   # (the direct kernels accumulate with atomics)
 
+    def _fwd_taps(self, x, tape):
+        N, D, H, W, C = x.shape
+        if N * D * H * W < self.GEMM_MIN_CELLS:
+            return self.fallback.fwd(x, tape)
+        self._sync()
+        k, s, p, op, d = self.tuple
+        P = self.taps_fwd.fprop(x, out_dtype=torch.float32, use_bias=False, out_channels_stride=(self.T + 3) // 4 * 4)     # [N, D, H, W, ld]
+        out = taps_fold(P, self.mod.bias, self.fallback_op.out_dims((D, H, W)), k, s, p, d).unsqueeze(-1)
+        if tape is not None:
+            tape.append((x,))
+        return out
+
+    def _bwd_taps(self, G, saved, grads, wgrad_only):
+        (x,) = saved
+        N, D, H, W, C = x.shape
+        if N * D * H * W < self.GEMM_MIN_CELLS:
+            return self.fallback.bwd(G, saved, grads, wgrad_only=wgrad_only)
+        self._sync()
+        k, s, p, op, d = self.tuple
+        G = G.float().contiguous().view(N, *self.fallback_op.out_dims((D, H, W)))
+        dw, db = grads.buf(self.mod.weight), grads.buf(self.mod.bias)
+        if debug.deterministic():
+            from ...engine import colsum_det
+            colsum_det(G.view(-1, 1), 1, db)     # bias gradient = sum of the gradient volume, in a fixed order
+            db = None
+        Gc = taps_unfold(G, x.dtype, (D, H, W), k, s, d, -p, self.taps_bwd.cs_in(), db=db)
+        dx = None
+        if not wgrad_only:
+            dx = self.taps_bwd.fprop(Gc, mask=x if self.in_act else None, mask_mode=MASK_POS if self.in_act else MASK_NONE, use_bias=False)
+        self.taps_fwd.wgrad(x, Gc, dw, None)
+        grads.done(self.mod.weight, self.mod.bias)
+        return dx
+
     def fwd(self, x, tape):
+        if not self.default:
+            return self._fwd_taps(x, tape)
         N, D, H, W, C = x.shape
         out = torch.empty((N, 2 * D, 2 * H, 2 * W, 1), dtype=torch.float32, device=x.device)
         lib, st = _ffi.lib(), _ffi.stream()
@@ -402,6 +518,8 @@ class _ConvT1Stage:
 
     def bwd(self, G, saved, grads, wgrad_only=False):
         """wgrad_only: the weight / bias gradient alone (`BaselineVQVAE.last_layer_grad`: im2col of the gradient + ONE wgrad launch, no data gradient)."""
+        if not self.default:
+            return self._bwd_taps(G, saved, grads, wgrad_only)
         (x,) = saved
         N, D, H, W, C = x.shape
         G = G.float().contiguous()
@@ -778,12 +896,14 @@ class BaselineVQVAE(VQVAEBase, nn.Module):
             # (baseline.py:274-282 builds SubpixelUpsample(in_channels=n_channels // 2): with one level the residual stack in front of it is n_channels wide and
             #  the reference itself fails in the first forward)
             raise NotImplementedError("use_subpixel_conv=True needs n_levels >= 2 and n_channels // 2 a multiple of 8")
-        for dp in downsample_parameters:
-            if dp[3] != 1:
-                raise NotImplementedError("dilation != 1")
-        for up in upsample_parameters:
-            if tuple(up) != (4, 2, 1, 0, 1):
-                raise NotImplementedError("upsample_parameters other than (4, 2, 1, 0, 1)")
+        for dp in downsample_parameters:      # (kernel, stride, padding, dilation): ValueError / NotImplementedError naming the tuple
+            if len(dp) != 4:
+                raise ValueError(f"downsample_parameters {tuple(dp)}: four numbers per level (kernel, stride, padding, dilation)")
+            conv_plan.check_tuple("conv", dp[0], dp[1], dp[2], 0, dp[3], flag="downsample_parameters")
+        for up in upsample_parameters:        # (kernel, stride, padding, output_padding, dilation)
+            if len(up) != 5:
+                raise ValueError(f"upsample_parameters {tuple(up)}: five numbers per level (kernel, stride, padding, output_padding, dilation)")
+            conv_plan.check_tuple("convT", up[0], up[1], up[2], up[3], up[4], flag="upsample_parameters")
         if n_res_channels != n_channels:
             raise NotImplementedError("n_res_channels != n_channels (configure.py:27-28 always passes them equal)")
         self.n_levels, self.downsample_parameters, self.upsample_parameters = n_levels, downsample_parameters, upsample_parameters
@@ -886,10 +1006,10 @@ class BaselineVQVAE(VQVAEBase, nn.Module):
         kernels for such operands) over the same parameters instead of failing with SA_EUNSUPPORTED."""
         if self.encoder_forward_dtype == self.compute_dtype:
             return self._enc_chain
-        k, s_, p_, _ = self.downsample_parameters[0]
+        k, s_, p_, d_ = self.downsample_parameters[0]
         vox = images.shape[0]
         for d in images.shape[2:]:
-            vox *= (d + 2 * p_ - k) // s_ + 1
+            vox *= conv_plan.out_size("conv", k, s_, p_, 0, d_, d)
         too_big = vox * self._level_width(0, decoder=False) * 2 >= 0xfffffff0 - 4096
         if not (too_big or (_ffi.lib().sa_get_debug_flags() & debug.LIB_FLAGS["no_dma"])):
             return self._enc_chain
