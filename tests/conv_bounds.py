@@ -22,6 +22,7 @@ import torch.nn.functional as F
 GAMMA = 2.0 ** -17
 U32 = 2.0 ** -24          # one fp32 rounding (bias / addend / final fp32 store)
 GELU_LIP = 1.13           # max |gelu'(x)| (erf form): the bound of a GELU epilogue scales by it
+SLOPE32 = float(torch.tensor(0.2, dtype=torch.float32))     # the LeakyReLU slope as the kernels get it (sa_epilogue.slope is a float)
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 _FMT = {"bf16": (7, -126), "f16": (10, -14)}     # (stored mantissa bits, minimum normal exponent)
@@ -85,6 +86,13 @@ def assert_bounded(what: str, got, ref, A, witness_ref, out: str = "f32", lip: f
     assert not wok, f"{what}: the planted defect is not detected at this shape (witness max|err|/A = {wratio:.2e})"
 
 
+def assert_witness_fails(what: str, got, witness_ref, A, out: str = "f32", lip: float = 1.0, extra=None, log=print):
+    """the witness half of assert_bounded alone: a further planted defect of an output that assert_bounded already held to its reference"""
+    wok, wratio, _ = check(got, witness_ref, A, out, lip, extra)
+    log(f"  {what}: witness max|err|/A = {wratio:.2e}, {'PASSES -- bound does not discriminate' if wok else 'fails as it must'}")
+    assert not wok, f"{what}: the planted defect is not detected at this shape (witness max|err|/A = {wratio:.2e})"
+
+
 # ------------------------------------------------------------------------------------------------------------------------------ references
 def conv_ref(kind, x, w, b, s, p):
     if kind == "conv":
@@ -123,14 +131,17 @@ def wgrad_last_plane(kind, x, g, wshape, s, p, k):
 # column-sum kernels after a weight gradient leave no log entry: tests/test_conv_bounds_gpu.py restates which of them run from their rule).
 #   op: fprop / dgrad / wgrad (ConvOp), bwd1x1 (engine.conv1x1_backward), resblock (_ResStage fused block), conv1 / convt1 (one-channel stages)
 #   epi: none (no bias) | bias | relu | add_relu (addend before ReLU, 16-bit output) | mask (addend, then a sign mask of the given tensor) | gelu
+#        | lrelu (forward: bias, then LeakyReLU 0.2) | mask_lrelu (data gradient: x 1 where the given tensor is > 0, x 0.2 elsewhere -- +0.0 and -0.0
+#        planted in it; no addend).  Both also fail the same reference with slope 0 (ReLU / the sign mask), mask_lrelu the one that tests mask >= 0.
+#   out_stride: channel stride of the forward output (the discriminator's last layer writes cout = 1 unpadded)
 #   acc: weight gradients accumulate into non-zero dw / db
 BF, H, F32 = "bf16", "f16", "f32"
 DMA = "conv_fprop_dma_kernel"
 
 
-def _c(id, op, kind, cin, cout, k, s, p, N, dims, dt, out, epi, kernels, flags=None, fwd=None, acc=False):
+def _c(id, op, kind, cin, cout, k, s, p, N, dims, dt, out, epi, kernels, flags=None, fwd=None, acc=False, out_stride=None):
     return dict(id=id, op=op, kind=kind, cin=cin, cout=cout, k=k, s=s, p=p, N=N, dims=dims, dt=dt, fwd=fwd or dt, out=out, epi=epi,
-                kernels=list(kernels), flags=dict(flags or {}), acc=acc)
+                kernels=list(kernels), flags=dict(flags or {}), acc=acc, out_stride=out_stride)
 
 
 # 3x3x3 stride-1 grids the halo kernels take: (D, H, W) with N = 2
@@ -235,6 +246,21 @@ CASES = [
        ["convt1_fwd_kernel<bf16_t>", "convt1_dgrad_kernel<bf16_t>", "convt1_wgrad_kernel<bf16_t>"]),
     _c("convt1_direct_f32", "convt1", "convT", 128, 1, 4, 2, 1, 2, (3, 5, 7), F32, F32, "bias",
        ["convt1_fwd_kernel<float>", "convt1_dgrad_kernel<float>", "convt1_wgrad_kernel<float>"]),
+    # ---- the PatchGAN discriminator's own paths (networks/discriminator/baseline.py): the LeakyReLU of the forward epilogue and of the data-gradient
+    #      mask in each of the three epilogue bodies (csrc/conv_fprop_common.h: batched LDS body, row-at-a-time body, register body), and its
+    #      stride-1 k4 layers -- the last one with cout = 1 (fp32 output at channel stride 1; its gradient arrives 8 wide with one valid channel)
+    _c("disc_first_layer_lrelu", "fprop", "conv", 1, 64, 4, 2, 1, 2, (8, 10, 12), BF, BF, "lrelu", [f"{DMA}<unsigned short, 4, 1, 2, 4, false, false, 1>"]),
+    _c("fprop_dma_16col_f32_lrelu", "fprop", "conv", 16, 12, 4, 2, 1, 2, (8, 10, 12), F32, F32, "lrelu", [f"{DMA}<float, 4, 1, 2, 1, false, false, 1>"]),
+    _c("fprop_cells256_conv_lrelu", "fprop", "conv", 64, 128, 4, 2, 1, 2, CELLS, BF, BF, "lrelu", ["conv_fprop_cells256_kernel<unsigned short>"]),
+    _c("dgrad_stride2_classes_mask_lrelu", "dgrad", "conv", 32, 40, 4, 2, 1, 2, (8, 10, 12), BF, F32, "mask_lrelu",
+       [f"{DMA}<unsigned short, 4, 1, 2, 2, false, false, 1>"]),
+    _c("dgrad_stride2_cells256_mask_lrelu", "dgrad", "conv", 128, 64, 4, 2, 1, 2, CELLS, BF, BF, "mask_lrelu", ["conv_fprop_cells256_kernel<unsigned short>"]),
+    _c("disc_k4s1_fprop", "fprop", "conv", 32, 40, 4, 1, 1, 2, (6, 7, 9), BF, BF, "bias", [f"{DMA}<unsigned short, 4, 1, 2, 4, false, false, 1>"]),
+    _c("disc_k4s1_dgrad", "dgrad", "conv", 32, 40, 4, 1, 1, 2, (6, 7, 9), BF, BF, "mask_lrelu", [f"{DMA}<unsigned short, 4, 1, 2, 2, false, false, 1>"]),
+    _c("disc_k4s1_wgrad", "wgrad", "conv", 32, 40, 4, 1, 1, 2, (6, 7, 9), BF, F32, "bias", ["conv_wgrad_dma_kernel<unsigned short, false, 8>", "wgrad_reduce_kernel"], acc=True),
+    _c("disc_last_layer_fprop", "fprop", "conv", 64, 1, 4, 1, 1, 2, (6, 7, 9), BF, F32, "bias", [f"{DMA}<unsigned short, 4, 1, 2, 1, true, false, 1>"], out_stride=1),
+    _c("disc_last_layer_dgrad", "dgrad", "conv", 64, 1, 4, 1, 1, 2, (6, 7, 9), BF, BF, "mask_lrelu", [f"{DMA}<unsigned short, 4, 1, 2, 4, false, false, 1>"]),
+    _c("disc_last_layer_wgrad", "wgrad", "conv", 64, 1, 4, 1, 1, 2, (6, 7, 9), BF, F32, "bias", ["conv_wgrad_dma_kernel<unsigned short, false, 8>", "wgrad_reduce_kernel"], acc=True),
 ]
 
 # the split-count tunables (read once per process: csrc/elementwise.hip tunables_from_env): every setting runs the wgrad_halo9 case in a fresh child

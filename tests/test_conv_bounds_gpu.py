@@ -48,9 +48,15 @@ def _kernels(names, case):
         assert any(n.startswith(want) for n in got), f"{case['id']}: expected a launch of {want!r}, the log holds {got}"
 
 
-def _epilogue(z, case, add=None, mask=None):
-    """the reference epilogue on the fp64 pre-activation z (bias included); returns (out, lip, extra)"""
+def _epilogue(z, case, add=None, mask=None, slope=cb.SLOPE32, mask_ge=False):
+    """the reference epilogue on the fp64 pre-activation z (bias included); returns (out, lip, extra).  slope / mask_ge: the LeakyReLU witnesses
+    (slope 0: what ReLU or the sign mask would give; mask_ge: the mask tested with >= 0, which lets +0.0 and -0.0 through)"""
     epi = case["epi"]
+    if epi == "lrelu":
+        return torch.where(z > 0, z, slope * z), 1.0, None
+    if epi == "mask_lrelu":
+        keep = (mask >= 0) if mask_ge else (mask > 0)
+        return z * torch.where(keep, 1.0, slope), 1.0, None
     if epi in ("none", "bias"):
         return z, 1.0, None
     if epi == "relu":
@@ -66,7 +72,35 @@ def _epilogue(z, case, add=None, mask=None):
 
 def _ffi_consts():
     from synthanatomy_amd import _ffi
-    return dict(none=_ffi.ACT_NONE, bias=_ffi.ACT_NONE, relu=_ffi.ACT_RELU, gelu=_ffi.ACT_GELU, add_relu=_ffi.ACT_RELU, mask=_ffi.ACT_NONE)
+    return dict(none=_ffi.ACT_NONE, bias=_ffi.ACT_NONE, relu=_ffi.ACT_RELU, gelu=_ffi.ACT_GELU, add_relu=_ffi.ACT_RELU, mask=_ffi.ACT_NONE,
+                lrelu=_ffi.ACT_LRELU, mask_lrelu=_ffi.ACT_NONE)
+
+
+def _padded(t, width):
+    """channels-last t zero-padded to `width` channels (engine.cast_pad's layout: a cin = 1 input, a cout = 1 gradient)"""
+    return t if t.shape[-1] == width else F.pad(t, (0, width - t.shape[-1]))
+
+
+def _plant_zeros(mask, z):
+    """+0.0 and -0.0 in the channels-last mask at the eight voxels where |z| (fp64, NCDHW) is largest, alternating"""
+    flat = mask.view(-1)
+    top = torch.topk(_cl(z).reshape(-1).abs(), 8).indices
+    flat[top[0::2]] = 0.0
+    flat[top[1::2]] = -0.0
+
+
+def _lrelu_witnesses(what, got, z, case, A, out, mask64=None):
+    """a LeakyReLU row must also fail the reference with slope 0 and, for the data-gradient mask, the one that tests mask >= 0 -- on every 61st
+    element and the planted zeros (failing on a part is failing; the whole of a cells256 volume would cost half its row again)"""
+    if case["epi"] not in ("lrelu", "mask_lrelu"):
+        return
+    sel = torch.arange(0, z.numel(), 61)
+    if mask64 is not None:
+        sel = torch.cat([sel, (mask64.reshape(-1) == 0).nonzero().flatten()])
+    got, z, A, mask64 = (None if t is None else t.reshape(-1)[sel] for t in (got, z, A, mask64))
+    cb.assert_witness_fails(what + " [slope 0]", got, _epilogue(z, case, None, mask64, slope=0.0)[0], A, out)
+    if case["epi"] == "mask_lrelu":
+        cb.assert_witness_fails(what + " [mask >= 0]", got, _epilogue(z, case, None, mask64, mask_ge=True)[0], A, out)
 
 
 def _check16(what, got, ref, A, wit, out, lip=1.0, extra=None):
@@ -100,9 +134,10 @@ def _fprop(case, gen):
         mask = _operand((N, *od, case["cout"]), case["dt"], gen)
     use_bias = case["epi"] != "none"
     with debug.override(**case["flags"]), _ffi.kernel_log() as names:
-        y = op.fprop(x.to(DEV).to(cb.DT[fdt]), act=_ffi_consts()[case["epi"]], addend=None if add is None else add.to(DEV).to(cb.DT[fdt]),
+        y = op.fprop(_padded(x, op.cs_in()).to(DEV).to(cb.DT[fdt]), act=_ffi_consts()[case["epi"]], addend=None if add is None else add.to(DEV).to(cb.DT[fdt]),
                      add_before_act=case["epi"] == "add_relu", mask=None if mask is None else mask.to(DEV).to(cb.DT[case["dt"]]),
-                     mask_mode=_ffi.MASK_POS if mask is not None else _ffi.MASK_NONE, out_dtype=cb.DT[out], use_bias=use_bias)
+                     mask_mode=_ffi.MASK_POS if mask is not None else _ffi.MASK_NONE, out_dtype=cb.DT[out], use_bias=use_bias,
+                     out_channels_stride=case["out_stride"], slope=cb.SLOPE32)
         torch.cuda.synchronize()
     _kernels(names, case)
     x64, w64 = _ncdhw(x), w.double()
@@ -120,6 +155,7 @@ def _fprop(case, gen):
     ref, lip, extra = _epilogue(z, case, add64, mask64)
     wit, _, _ = _epilogue(z - dz, case, add64, mask64)
     _check16(f"[{case['id']}] y", _ncdhw(y), ref, A, wit, out, lip, extra)
+    _lrelu_witnesses(f"[{case['id']}] y", _ncdhw(y), z, case, A, out)
 
 
 def _dgrad(case, gen):
@@ -134,14 +170,19 @@ def _dgrad(case, gen):
     if case["epi"] == "mask":           # the residual block's data gradient: + the incoming gradient, masked by the layer input's sign
         add = _operand((N, *dims, case["cin"]), dt, gen)
         mask = _operand((N, *dims, case["cin"]), dt, gen)
-    with debug.override(**case["flags"]), _ffi.kernel_log() as names:
-        dx = op.dgrad(g.to(DEV).to(cb.DT[dt]), dims, addend=None if add is None else add.to(DEV).to(cb.DT[dt]),
-                      mask=None if mask is None else mask.to(DEV).to(cb.DT[dt]), mask_mode=_ffi.MASK_POS if mask is not None else _ffi.MASK_NONE,
-                      out_dtype=cb.DT[out])
-        torch.cuda.synchronize()
-    _kernels(names, case)
     g64, w64 = _ncdhw(g), w.double()
     z = cb.dgrad_ref(kind, g64, w64, s, p, dims)
+    mode = _ffi.MASK_POS if mask is not None else _ffi.MASK_NONE
+    if case["epi"] == "mask_lrelu":     # the discriminator's data gradient: LeakyReLU'(the layer input), both signs and both zeros in the mask
+        mask = _operand((N, *dims, case["cin"]), dt, gen)
+        _plant_zeros(mask, z)
+        mode = _ffi.MASK_LRELU
+    with debug.override(**case["flags"]), _ffi.kernel_log() as names:
+        # (a gradient whose channel count is no multiple of the vector arrives zero-padded to one, as engine.cast_pad leaves it)
+        dx = op.dgrad(_padded(g, -(-case["cout"] // op.vec) * op.vec).to(DEV).to(cb.DT[dt]), dims, addend=None if add is None else add.to(DEV).to(cb.DT[dt]),
+                      mask=None if mask is None else mask.to(DEV).to(cb.DT[dt]), mask_mode=mode, out_dtype=cb.DT[out], slope=cb.SLOPE32)
+        torch.cuda.synchronize()
+    _kernels(names, case)
     A = cb.dgrad_ref(kind, g64.abs(), w64.abs(), s, p, dims)
     if kind == "conv":   # witness: the last channel of the incoming gradient dropped
         dz = cb.dgrad_ref(kind, g64[:, -1:], w64[-1:], s, p, dims)
@@ -150,9 +191,11 @@ def _dgrad(case, gen):
     add64 = None if add is None else _ncdhw(add)
     if add64 is not None:
         A = A + add64.abs()
-    ref, lip, extra = _epilogue(z, case, add64, None if mask is None else _ncdhw(mask))
-    wit, _, _ = _epilogue(z - dz, case, add64, None if mask is None else _ncdhw(mask))
+    mask64 = None if mask is None else _ncdhw(mask)
+    ref, lip, extra = _epilogue(z, case, add64, mask64)
+    wit, _, _ = _epilogue(z - dz, case, add64, mask64)
     _check16(f"[{case['id']}] dx", _ncdhw(dx), ref, A, wit, out, lip, extra)
+    _lrelu_witnesses(f"[{case['id']}] dx", _ncdhw(dx), z, case, A, out, mask64)
 
 
 def _wgrad_inputs(case, gen):
@@ -227,9 +270,10 @@ def _wgrad(case, gen):
                 dx = engine.conv1x1_backward(op, x.to(DEV).to(dt), g.to(DEV).to(dt), dw, db)
                 assert dx is not None
             else:
-                op.wgrad(x.to(DEV).to(dt), g.to(DEV).to(dt), dw, db)
+                gp = _padded(g, -(-case["cout"] // op.vec) * op.vec)      # (a cout = 1 gradient arrives 8 wide with one valid channel)
+                op.wgrad(_padded(x, op.cs_in()).to(DEV).to(dt), gp.to(DEV).to(dt), dw, db)
             torch.cuda.synchronize()
-        helpers = _wgrad_helpers(op, x, g, names, True)      # (the log is read when its block closes)
+        helpers = _wgrad_helpers(op, x, gp if case["op"] != "bwd1x1" else g, names, True)      # (the log is read when its block closes)
     print(f"[{case['id']}] reduce / column-sum kernels by rule: {', '.join(sorted(helpers))}")
     _kernels(list(names) + sorted(helpers), case)
     refs = _wgrad_refs(case, w, x, g, dw0, db0)
