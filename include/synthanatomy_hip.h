@@ -100,6 +100,7 @@ int sa_kernel_log_read(char *buf, int cap, int stop);
 #define SA_DBG_NO_CELLS256       (1u << 21)  /* stride-2 family on the im2col-order kernel instead of the 256-voxel cell mainloop (conv_fprop_cells256_kernel): A/B + cross-family tests */
 #define SA_DBG_NO_CLASS_LAUNCH    (1u << 22)  /* sa_conv_fprop_classes answers SA_EUNSUPPORTED: the parity classes of a transposed convolution as separate launches (A/B, equality test) */
 #define SA_DBG_NO_STRIP_TILES     (1u << 23)  /* two-plane 3x3x3 halo tiles: the last 1..8 columns of a plane on ordinary 8 x 16 tiles instead of 16 x 8 strip tiles (A/B, equality test) */
+#define SA_DBG_GENERIC_EPILOGUE   (1u << 24)  /* register epilogue of the eight-wave halo / cell kernels: the generic code instead of the launch's compile-time recipe (A/B, equality test) */
 #define SA_DBG_FAVOR_SEQ_ALWAYS (1u << 18)  /* FAVOR+ chunk states in the sequential form for every batch (default: from 40 (batch, head) pairs; tests) */
 #define SA_DBG_DETERMINISTIC     (1u << 16)  /* fixed-order reductions where the library itself chooses (BatchNorm sums); see the deterministic-mode section */
 #define SA_DBG_SCAN_EXACT_SHIFT  10          /* 3 bits: chunk states | scan A outputs | scan B outputs on the exact-fp32 MFMA kernels */
@@ -111,6 +112,10 @@ int sa_bench_mfma_bf16(float *scratch, int blocks, int iters, void *stream);
 int sa_bench_mfma_bf16_ex(float *scratch, int blocks, int threads, int iters, int shape, void *stream);
 uint32_t sa_get_debug_flags(void);
 uint32_t sa_set_debug_flags(uint32_t flags);
+/* test aid: the epilogue recipe (1..7, csrc/conv_fprop_common.h) a launch with this epilogue takes in the eight-wave 3x3x3 halo and stride-2 cell kernels
+ * under the current debug flags, 0 = the generic epilogue code.  dtype: the launch's operand type (SA_BF16 / SA_F16).  Evaluates the kernels' own rule
+ * (a kernel compiled without that recipe -- recipe 5 is in the fused f16 block only, the fused block carries 4 / 5 only, its strip-tile instance none -- runs the generic code all the same). */
+int sa_epilogue_recipe(const sa_epilogue *ep, int dtype);
 
 /* ---- weights: reference layout (fp32 nn.Parameter) -> packed [CoutPad][Kpad] GEMM operand ------------------------
  * element (row r, reduce channel c, tap t) is read at  w[r*s_row + c*s_red + tap_lut[t]]  (tap_lut NULL = identity).

@@ -81,6 +81,7 @@ _SIGS = {
     "sa_bench_mfma_bf16_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sa_get_debug_flags": (ctypes.c_uint32, []),
     "sa_set_debug_flags": (ctypes.c_uint32, [ctypes.c_uint32]),
+    "sa_epilogue_recipe": (c_int, [POINTER(Epilogue), c_int]),
     "sa_conv1_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sa_conv1_fwd_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sa_conv1_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

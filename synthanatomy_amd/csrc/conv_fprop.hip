@@ -43,7 +43,7 @@ static int conv_fprop_impl(const sa_conv_geom* g, int ncls, int dtype, const voi
     a.w2pk = nullptr;
     a.bias1 = nullptr;
     a.h_out = nullptr;
-    a.dbg = g_tunables.pp_dbg;
+    a.dbg = g_tunables.pp_dbg | (dbg(SA_DBG_GENERIC_EPILOGUE) ? FPROP_DBG_GENERIC_EPILOGUE : 0u);
     a.group_m = 0;
     a.ncls = 0;
     for (int c = 0; c < 8; ++c) {
@@ -81,6 +81,11 @@ extern "C" int sa_conv_fprop(const sa_conv_geom* g, int dtype, const void* in, c
                              void* stream) {
     if (!g || !in || !wpk || !out || !ep) return SA_EINVAL;
     return conv_fprop_impl(g, 0, dtype, in, &wpk, out, ep, stream);
+}
+
+extern "C" int sa_epilogue_recipe(const sa_epilogue* ep, int dtype) {
+    if (!ep || (dtype != SA_BF16 && dtype != SA_F16)) return 0;
+    return sa::epi_recipe_id(*ep, dtype == SA_F16, sa::dbg(SA_DBG_GENERIC_EPILOGUE));
 }
 
 // The launch geometries of ONE layer that differ only in in_off / out_off and their packed operands -- the eight output-parity classes of
@@ -135,7 +140,7 @@ extern "C" int sa_resblock_fprop(const sa_conv_geom* g, int dtype, const void* x
     a.w2pk = w1pk;
     a.bias1 = bias1;
     a.h_out = h_out;
-    a.dbg = 0;
+    a.dbg = dbg(SA_DBG_GENERIC_EPILOGUE) ? FPROP_DBG_GENERIC_EPILOGUE : 0u;
     a.group_m = 0;
     a.ncls = 0;
     return dtype == SA_F16 ? launch_resblock_f16(a, (hipStream_t)stream) : launch_resblock<bf16_t>(a, (hipStream_t)stream);

@@ -417,13 +417,57 @@ __device__ __forceinline__ void epi_unpack16(const u32x4 (&p)[W], float (&v)[16]
     }
 }
 
+// ---- epilogue recipes.  The register epilogue is specialised at compile time on the PRESENCE and width of addend and mask, but what it does with them --
+// activation, addend before or after it, mask mode, output type, bf16 copy -- are run-time fields of sa_epilogue, and tested per element they turn the
+// 16-element loop of every row group into a chain of tiny basic blocks (halo256 bf16: 86 755 instructions, 7 053 conditional branches, one 32-MFMA block of
+// main loop).  A RECIPE fixes those fields at compile time for the combinations the VQ-VAE training step sends through the eight-wave halo / cell kernels;
+// inside one the element loop has no run-time test on any sa_epilogue field.  A recipe runs the operations of the generic code for its field values, in the
+// same order -- bit-identical results -- and requires alpha == nullptr: the generic code then multiplies by 1.0f, which is exact, so the multiply is dropped.
+// Every other launch (LeakyReLU, GELU, ReZero alpha, fp32 outputs / addends / masks, ...) takes the generic code: EpiGeneric.
+struct EpiGeneric {
+    static constexpr bool fixed = false;
+    static constexpr int act = SA_ACT_NONE, mask_mode = SA_MASK_NONE;
+    static constexpr bool add_first = false, lp = false;
+};
+template <int ACT, bool ADD_FIRST, int MASK_MODE, bool LP>
+struct EpiRecipe {
+    static constexpr bool fixed = true;
+    static constexpr int act = ACT, mask_mode = MASK_MODE;
+    static constexpr bool add_first = ADD_FIRST, lp = LP;
+};
+// FpropArgs.dbg: take the generic epilogue whatever the launch (SA_DBG_GENERIC_EPILOGUE of the library's debug word, set by the launchers)
+constexpr uint32_t FPROP_DBG_GENERIC_EPILOGUE = 1u << 30;
+// Recipe of a launch's epilogue in a kernel of a bf16 (f16io = false) or f16 forward (f16io = true) chain, 0: none (generic code).  Block-uniform; also what
+// sa_epilogue_recipe answers on the host.
+//   bf16  1: data gradient, bf16 addend added last, MASK_POS bf16 mask     2: the same without a mask      3: MASK_POS bf16 mask, no addend
+//         4: ReLU, bf16 addend added first                                 6: ReLU, no addend
+//   f16   5: ReLU, f16 addend added first, bf16 copy of the output         7: ReLU, no addend, bf16 copy of the output
+__host__ __device__ __forceinline__ int epi_recipe_id(const sa_epilogue& ep, bool f16io, bool force_generic) {
+    if (force_generic || ep.alpha != nullptr || ep.out_pre != nullptr) return 0;
+    const bool add = ep.addend != nullptr, mask = ep.mask_mode != SA_MASK_NONE;
+    if (ep.out_dtype != (f16io ? SA_F16 : SA_BF16) || (add && ep.add_dtype == SA_F32)) return 0;
+    if (mask && (ep.mask_mode != SA_MASK_POS || ep.mask_dtype == SA_F32)) return 0;
+    if (f16io) {
+        if (ep.act != SA_ACT_RELU || mask || ep.out_lp == nullptr) return 0;
+        return !add ? 7 : (ep.add_before_act ? 5 : 0);
+    }
+    if (ep.act == SA_ACT_RELU) return mask ? 0 : (!add ? 6 : (ep.add_before_act ? 4 : 0));
+    if (ep.act != SA_ACT_NONE) return 0;
+    if (add) return ep.add_before_act ? 0 : (mask ? 1 : 2);
+    return mask ? 3 : 0;
+}
+
 // one batch: row groups JB .. JB + EPI_BATCH - 1 (compile-time indices: a run-time index would demote the accumulators to scratch memory)
 // F16IO (the kernels of an f16 forward chain): 16-bit addends and outputs are IEEE halves, and the launch may ask for a bf16 copy of its output
 // (sa_epilogue.out_lp); compile-time, because the eight-wave bf16 kernels sit exactly at the 128-VGPR line and must not carry the extra paths
-template <int MI, int NI, int JB, bool ADD, bool MASK, bool ADD32, bool MASK32, int BUDGET, bool F16IO, typename RowOv>
+// R: the launch's recipe (EpiRecipe: the switches below are compile-time constants) or EpiGeneric (they are the run-time fields of sa_epilogue)
+template <int MI, int NI, int JB, bool ADD, bool MASK, bool ADD32, bool MASK32, int BUDGET, bool F16IO, typename R, typename RowOv>
 __device__ __forceinline__ void epi_batch(const FpropArgs& a, float4_t (&acc)[NI][MI], uint32_t wm, uint32_t frow, uint32_t c0, RowOv row_ov, float alpha) {
     const sa_conv_geom& g = a.g;
     const sa_epilogue& ep = a.ep;
+    const int act = R::fixed ? R::act : ep.act, mask_mode = R::fixed ? R::mask_mode : ep.mask_mode;
+    const bool add_first = R::fixed ? R::add_first : ep.add_before_act != 0;
+    const bool out32 = !R::fixed && ep.out_dtype == SA_F32, out_lp = R::fixed ? R::lp : ep.out_lp != nullptr;
     constexpr int AW = ADD32 ? 4 : 2, MW = MASK32 ? 4 : 2;
     constexpr int EPI_BATCH = epi_batch_size<ADD, MASK, ADD32, MASK32, BUDGET>();
     u32x4 adp[EPI_BATCH][AW], mkp[EPI_BATCH][MW];
@@ -464,21 +508,21 @@ __device__ __forceinline__ void epi_batch(const FpropArgs& a, float4_t (&acc)[NI
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             float x = v[e];
-            if constexpr (ADD) { if (ep.add_before_act) x += ad[e]; }
-            if (ep.act == SA_ACT_RELU) x = fmaxf(x, 0.f);
-            else if (ep.act == SA_ACT_LRELU) x = x > 0.f ? x : x * ep.slope;
-            else if (ep.act == SA_ACT_GELU) x = gelu_f(x);
-            x *= alpha;
-            if constexpr (ADD) { if (!ep.add_before_act) x += ad[e]; }
+            if constexpr (ADD) { if (add_first) x += ad[e]; }
+            if (act == SA_ACT_RELU) x = fmaxf(x, 0.f);
+            else if (act == SA_ACT_LRELU) x = x > 0.f ? x : x * ep.slope;
+            else if (act == SA_ACT_GELU) x = gelu_f(x);
+            if constexpr (!R::fixed) x *= alpha;      // (a recipe: alpha == nullptr, the generic code multiplies by 1.0f)
+            if constexpr (ADD) { if (!add_first) x += ad[e]; }
             if constexpr (MASK) {
-                if (ep.mask_mode == SA_MASK_POS) x = mk[e] > 0.f ? x : 0.f;
-                else if (ep.mask_mode == SA_MASK_LRELU) x = mk[e] > 0.f ? x : x * ep.slope;
-                else if (ep.mask_mode == SA_MASK_GELU) x *= gelu_grad_f(mk[e]);
+                if (mask_mode == SA_MASK_POS) x = mk[e] > 0.f ? x : 0.f;
+                else if (mask_mode == SA_MASK_LRELU) x = mk[e] > 0.f ? x : x * ep.slope;
+                else if (mask_mode == SA_MASK_GELU) x *= gelu_grad_f(mk[e]);
             }
             v[e] = x;
         }
         if (ok[jj]) {
-            if (ep.out_dtype == SA_F32) {
+            if (out32) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) *(float4_t*)((float*)a.out + o[jj] + 4 * k) = (float4_t){v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
             } else if constexpr (F16IO) {
@@ -493,7 +537,7 @@ __device__ __forceinline__ void epi_batch(const FpropArgs& a, float4_t (&acc)[NI
                         pl[e] = pack2<bf16_t>(v[8 * k + 2 * e], v[8 * k + 2 * e + 1]);
                     }
                     *(u32x4*)((bf16_t*)a.out + o[jj] + 8 * k) = pk;
-                    if (ep.out_lp) *(u32x4*)((bf16_t*)ep.out_lp + o[jj] + 8 * k) = pl;
+                    if (out_lp) *(u32x4*)((bf16_t*)ep.out_lp + o[jj] + 8 * k) = pl;
                 }
             } else {
 #pragma unroll
@@ -521,20 +565,63 @@ __device__ __forceinline__ void epi_add_bias(const FpropArgs& a, float4_t (&acc)
 }
 
 // all batches of one (ADD, MASK, widths) specialisation
-template <int MI, int NI, int JB, bool ADD, bool MASK, bool ADD32, bool MASK32, int BUDGET, bool F16IO, typename RowOv>
+template <int MI, int NI, int JB, bool ADD, bool MASK, bool ADD32, bool MASK32, int BUDGET, bool F16IO, typename R, typename RowOv>
 __device__ __forceinline__ void epi_run_from(const FpropArgs& a, float4_t (&acc)[NI][MI], uint32_t wm, uint32_t frow, uint32_t c0, RowOv row_ov, float alpha) {
     if constexpr (JB < MI) {
-        epi_batch<MI, NI, JB, ADD, MASK, ADD32, MASK32, BUDGET, F16IO>(a, acc, wm, frow, c0, row_ov, alpha);
-        epi_run_from<MI, NI, JB + epi_batch_size<ADD, MASK, ADD32, MASK32, BUDGET>(), ADD, MASK, ADD32, MASK32, BUDGET, F16IO>(a, acc, wm, frow, c0, row_ov, alpha);
+        epi_batch<MI, NI, JB, ADD, MASK, ADD32, MASK32, BUDGET, F16IO, R>(a, acc, wm, frow, c0, row_ov, alpha);
+        epi_run_from<MI, NI, JB + epi_batch_size<ADD, MASK, ADD32, MASK32, BUDGET>(), ADD, MASK, ADD32, MASK32, BUDGET, F16IO, R>(a, acc, wm, frow, c0, row_ov, alpha);
     }
 }
-template <int MI, int NI, bool ADD, bool MASK, bool ADD32, bool MASK32, int BUDGET, bool F16IO, typename RowOv>
+template <int MI, int NI, bool ADD, bool MASK, bool ADD32, bool MASK32, int BUDGET, bool F16IO, typename R = EpiGeneric, typename RowOv>
 __device__ __forceinline__ void epi_run(const FpropArgs& a, float4_t (&acc)[NI][MI], uint32_t wm, uint32_t frow, uint32_t c0, RowOv row_ov, float alpha) {
     static_assert(MI % 4 == 0, "row groups per wave must be a multiple of the largest batch");
-    epi_run_from<MI, NI, 0, ADD, MASK, ADD32, MASK32, BUDGET, F16IO>(a, acc, wm, frow, c0, row_ov, alpha);
+    epi_run_from<MI, NI, 0, ADD, MASK, ADD32, MASK32, BUDGET, F16IO, R>(a, acc, wm, frow, c0, row_ov, alpha);
 }
 
-template <int MI, int NI, int BUDGET = 64, bool F16IO = false, typename RowOv>
+// the recipes of a bf16 (1, 2, 3, 4, 6) or f16 forward (5, 7) kernel: `rcp` is block-uniform and one of those in RCPS
+#ifdef SA_EPI_MARKERS   // dev (tools/epilogue_paths.py): assembler comments around every recipe's code, no instruction
+#define SA_EPI_MARK(what, r) asm volatile("; SA_RECIPE_" what " " #r)
+#else
+#define SA_EPI_MARK(what, r)
+#endif
+#define SA_EPI_CASE(r, ADD, MASK, ...)                                                                                           \
+    case r:                                                                                                                      \
+        if constexpr ((RCPS >> r) & 1u) {                                                                                        \
+            SA_EPI_MARK("BEGIN", r);                                                                                             \
+            epi_run<MI, NI, ADD, MASK, false, false, BUDGET, F16IO, EpiRecipe<__VA_ARGS__>>(a, acc, wm, frow, c0, row_ov, 1.f); \
+            SA_EPI_MARK("END", r);                                                                                               \
+            return;                                                                                                              \
+        } else                                                                                                                   \
+            __builtin_unreachable();
+// RCPS: bit r = recipe r is compiled into this kernel (the caller tests it before the call)
+template <int MI, int NI, int BUDGET, bool F16IO, uint32_t RCPS, typename RowOv>
+__device__ __forceinline__ void epi_run_recipe(int rcp, const FpropArgs& a, float4_t (&acc)[NI][MI], uint32_t wm, uint32_t frow, uint32_t c0, RowOv row_ov) {
+    if constexpr (!F16IO) {
+        switch (rcp) {
+            SA_EPI_CASE(1, true, true, SA_ACT_NONE, false, SA_MASK_POS, false)
+            SA_EPI_CASE(2, true, false, SA_ACT_NONE, false, SA_MASK_NONE, false)
+            SA_EPI_CASE(3, false, true, SA_ACT_NONE, false, SA_MASK_POS, false)
+            SA_EPI_CASE(4, true, false, SA_ACT_RELU, true, SA_MASK_NONE, false)
+            SA_EPI_CASE(6, false, false, SA_ACT_RELU, false, SA_MASK_NONE, false)
+            default: __builtin_unreachable();
+        }
+    } else {
+        switch (rcp) {
+            SA_EPI_CASE(5, true, false, SA_ACT_RELU, true, SA_MASK_NONE, true)
+            SA_EPI_CASE(7, false, false, SA_ACT_RELU, false, SA_MASK_NONE, true)
+            default: __builtin_unreachable();
+        }
+    }
+}
+#undef SA_EPI_CASE
+
+// RCPS (the eight-wave halo and cell kernels): the recipes compiled into the kernel, bit r = recipe r -- EPI_RECIPES_PLAIN (1, 2, 3, 4, 6 and 7: what the
+// training step sends through the plain halo kernels and the cell kernel), or EPI_RECIPES_FUSED for the fused residual block, whose epilogue is
+// ReLU(addend + .) and nothing else (recipes 4 / 5: 5 is compiled into the fused f16 kernels only; other recipes' code would only add to kernels that sit
+// at the 128-VGPR line).  One block-uniform test at the entry sends a launch that matches one of them to that recipe's straight-line code; every other launch,
+// and every kernel with RCPS = 0, runs the generic code below as it was
+constexpr uint32_t EPI_RECIPES_PLAIN = 0xdeu, EPI_RECIPES_FUSED = (1u << 4) | (1u << 5);
+template <int MI, int NI, int BUDGET = 64, bool F16IO = false, uint32_t RCPS = 0u, typename RowOv>
 __device__ __forceinline__ void fprop_epilogue_regs(const FpropArgs& a, float4_t (&acc)[NI][MI], uint32_t wm, uint32_t wn, uint32_t frow, uint32_t fq,
                                                     uint32_t n_base, RowOv row_ov, bool bias_done = false) {
     static_assert(NI == 4, "4 column fragments per wave");
@@ -542,6 +629,13 @@ __device__ __forceinline__ void fprop_epilogue_regs(const FpropArgs& a, float4_t
     const float alpha = ep.alpha ? *ep.alpha : 1.f;
     if (!bias_done) epi_add_bias<MI, NI>(a, acc, wn, fq, n_base);
     const uint32_t c0 = n_base + wn * 64 + fq * 16;   // this lane's 16 channels after the transpose
+    if constexpr (RCPS != 0u) {
+        const int rcp = epi_recipe_id(ep, F16IO, (a.dbg & FPROP_DBG_GENERIC_EPILOGUE) != 0u);
+        if ((RCPS >> rcp) & 1u) {
+            epi_run_recipe<MI, NI, BUDGET, F16IO, RCPS>(rcp, a, acc, wm, frow, c0, row_ov);
+            return;
+        }
+    }
     const bool add = ep.addend != nullptr, mask = ep.mask_mode != SA_MASK_NONE;
     const bool a32 = ep.add_dtype == SA_F32, m32 = ep.mask_dtype == SA_F32;
     // block-uniform dispatch to a straight-line specialisation (loads of a batch back to back)

@@ -927,7 +927,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_fprop_halo256_kernel(con
                 for (int j = 0; j < MI; ++j) mma_slab<T>(acc[i][j], w2[i][NW == 4 ? ks : 0], xf[j]);
         }
     }
-    fprop_epilogue_regs<MI, NI, (NW == 4 ? 64 : SA_EPI_BUDGET8), std::is_same<T, f16_t>::value>(a, acc, wm, wn, frow, fq, n_base, row_vox);
+    // epilogue recipes: all of them in the plain eight-wave kernels, the fused block's own in the fused ones; none in the fused strip-tile instance, which
+    // sits at 128 VGPRs and spills 16 bytes more with any recipe compiled in (its launches are 2 % of the step)
+    fprop_epilogue_regs<MI, NI, (NW == 4 ? 64 : SA_EPI_BUDGET8), std::is_same<T, f16_t>::value, (NW != 8 || (FUSE && STRIP) ? 0u : FUSE ? EPI_RECIPES_FUSED : EPI_RECIPES_PLAIN)>(a, acc, wm, wn, frow, fq, n_base, row_vox);
 #ifdef SA_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     SA_T(t_end);
@@ -1116,7 +1118,7 @@ __global__ __launch_bounds__(512, 2) void conv_fprop_cells256_kernel(const Fprop
         if (d >= (uint32_t)g.Dm || h >= (uint32_t)g.Hm || w >= (uint32_t)g.Wm) return -1ll;
         return (((long long)pn * g.Do + (d * g.out_mult[0] + g.out_off[0])) * g.Ho + (h * g.out_mult[1] + g.out_off[1])) * g.Wo + (w * g.out_mult[2] + g.out_off[2]);
     };
-    fprop_epilogue_regs<MI, NI, SA_EPI_BUDGET8, std::is_same<T, f16_t>::value>(a, acc, wm, wn, frow, fq, n_base, row_vox);
+    fprop_epilogue_regs<MI, NI, SA_EPI_BUDGET8, std::is_same<T, f16_t>::value, EPI_RECIPES_PLAIN>(a, acc, wm, wn, frow, fq, n_base, row_vox);
 #endif
 }
 
