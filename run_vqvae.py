@@ -291,7 +291,7 @@ def training(cfg, rank, local, world, dev):
         disc = get_discriminator_network(dcfg).to(dev).train()
         d_flat = FlatParams(disc.parameters())
         d_opt = FusedAdam(d_flat, lr=cfg["discriminator_learning_rate"])
-        d_opt.on_step.append(lambda: [st.op.invalidate() for st in disc._stages])
+        d_opt.on_step.append(disc.invalidate_packed_weights)
         d_sched = ExponentialLR(d_opt, gamma=gamma)
         trainer = AdversarialTrainer(net, opt, get_generator_loss(cfg), loss_fn, disc, d_opt, get_discriminator_loss(cfg),
                                      use_adversarial_adaptive_weight=cfg["use_adversarial_adaptive_weight"],

@@ -445,6 +445,26 @@ class RangeRepacker:
         self._ranges, self._done = [], set()
 
 
+class Repack:
+    """A network's two ways to bring its packed GEMM operands up to date after the optimizer wrote the parameters through raw pointers.  ``ops_fn()`` lists the
+    network's ConvOps, in the same order every call (PackSet's descriptor table is keyed by it)."""
+
+    def __init__(self, ops_fn):
+        self.ops_fn, self._packset = ops_fn, PackSet()
+
+    def all(self):
+        """``opt.on_step``: invalidate every op and re-pack all operands in one launch"""
+        ops = self.ops_fn()
+        for op in ops:
+            op.invalidate()
+        self._packset.repack(ops)
+
+    def ranges(self, flat):
+        """``FusedAdam(in_backward=reducer)``: ``opt.on_range.append(r); opt.on_step.append(r.finish)`` INSTEAD of ``all`` -- the operands of a bucket are
+        re-packed right behind its optimizer slice, in the shadow of the backward pass"""
+        return RangeRepacker(flat, self.ops_fn)
+
+
 def colsum_det(g: torch.Tensor, C: int, db: torch.Tensor):
     """db[c] += sum over all rows of g[..., c] in a fixed order (sa_colsum_det)."""
     lib = _ffi.lib()

@@ -16,6 +16,7 @@ import torch.nn as nn
 from ... import _ffi
 from ..._ffi import ACT_LRELU, ACT_NONE, MASK_LRELU
 from ...engine import ConvOp, cast_pad, vec_of
+from ...runtime.backward import GradCtx
 
 SLOPE = 0.2
 
@@ -27,18 +28,6 @@ def weights_init(m):
     elif classname.find("BatchNorm") != -1:
         nn.init.normal_(m.weight.data, 1.0, 0.02)
         nn.init.constant_(m.bias.data, 0)
-
-
-class _GradCtx:
-    def __init__(self):
-        self.grads = {}
-
-    def buf(self, p):
-        if p is None:
-            return None
-        t = torch.zeros_like(p)
-        self.grads[p] = t
-        return t
 
 
 class _Stage:
@@ -123,7 +112,7 @@ class _DiscFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         net = ctx.net
-        gc = _GradCtx()
+        gc = GradCtx()
         G = gy.permute(0, 2, 3, 4, 1).contiguous()
         need_w = any(ctx.needs_input_grad[3:])
         for s, saved in zip(reversed(net._stages), reversed(ctx.tape)):
@@ -168,6 +157,11 @@ class BaselineDiscriminator(nn.Module):
 
     def _params(self):
         return [p for s in self._stages for p in s.params()]
+
+    def invalidate_packed_weights(self):
+        """Tell the stages that parameters were modified through raw pointers (fused Adam kernel); each op packs its operands again when it next runs."""
+        for s in self._stages:
+            s.op.invalidate()
 
     def forward(self, input):
         """Standard forward."""

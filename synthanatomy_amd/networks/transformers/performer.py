@@ -13,10 +13,8 @@ and running-state scans, fp32 rotary + banded local attention.  See oracle/perfo
 """
 from __future__ import annotations
 
-import collections
 import ctypes
 import math
-import os
 from enum import Enum
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -27,7 +25,8 @@ import torch.nn as nn
 from ... import _ffi, debug
 from ..._ffi import MASK_GELU
 from ... import engine as _engine
-from ...engine import ConvOp, PackSet
+from ...engine import ConvOp, Repack, _ru
+from ...runtime.backward import GradCtx, side_wgrad
 from .img2seq_ordering import Ordering
 from .transformer import TransformerBase, sequence_to_grid
 
@@ -36,14 +35,6 @@ class TransformerConditioningType(Enum):  # src/utils/transformer.py:21-24
     NONE = "none"
     BOSREPLACEMENT = "bos_replacement"
     PREPENDING = "prepending"
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
-
-
-def _ck(rc, what):
-    _ffi.check(rc, what)
 
 
 # ------------------------------------------------------------------------------------------------ parameter holders
@@ -131,7 +122,7 @@ class FastAttention(nn.Module):
         if pm.is_cuda:
             blocks = torch.randn(nblk, d, d, generator=generator, device=pm.device)
             rows = torch.randn(m, d, generator=generator, device=pm.device)
-            _ck(_ffi.lib().sa_favor_projection(_ffi.ptr(blocks), _ffi.ptr(rows), _ffi.ptr(pm), 1, nblk, m, d, _ffi.stream()), "sa_favor_projection")
+            _ffi.check(_ffi.lib().sa_favor_projection(_ffi.ptr(blocks), _ffi.ptr(rows), _ffi.ptr(pm), 1, nblk, m, d, _ffi.stream()), "sa_favor_projection")
         else:  # construction time on the host (before .to(device)); plain torch, not a compute fallback of the hot path
             blocks = torch.randn(nblk, d, d, generator=generator)
             q = torch.linalg.qr(blocks.transpose(1, 2))[0].transpose(1, 2).reshape(nblk * d, d)[:m]
@@ -214,7 +205,7 @@ class ProjectionUpdater(nn.Module):
                 blocks = torch.randn(nl * nblk, d_, d_, generator=gen, device=dev)
                 rows = torch.randn(nl * m_, d_, generator=gen, device=dev)
                 out = torch.empty(nl, m_, d_, device=dev)
-                _ck(_ffi.lib().sa_favor_projection(_ffi.ptr(blocks), _ffi.ptr(rows), _ffi.ptr(out), nl, nblk, m_, d_, _ffi.stream()), "sa_favor_projection")
+                _ffi.check(_ffi.lib().sa_favor_projection(_ffi.ptr(blocks), _ffi.ptr(rows), _ffi.ptr(out), nl, nblk, m_, d_, _ffi.stream()), "sa_favor_projection")
                 for i, mod in enumerate(mods):
                     mod.projection_matrix.copy_(out[i])
                     mod.projection_matrix._sa_epoch = getattr(mod.projection_matrix, "_sa_epoch", 0) + 1
@@ -285,9 +276,6 @@ def _cast(t, dtype):
     return cast_pad(t, dtype, t.shape[-1])
 
 
-_SIDE_STREAMS = {}
-
-
 def FAVOR_FWD_FLOP_PER_HEAD_ROW(m: int, dh: int) -> float:
     """ALGORITHMIC forward FLOPs of causal FAVOR+ per (batch, position, head): two feature maps 2 x 2 dh m, the state update k' (x) v and
     the read-out q' . S 2 x 2 m dh, the normaliser 2 x 2 m.  (The kernels execute about 3 x that on the matrix cores: split-bf16 products, and the key
@@ -310,97 +298,6 @@ def _favor_bracket_end(e0, key, flops):
     e1 = torch.cuda.Event(enable_timing=True)
     e1.record()
     _engine.TIMER.pending.append((key, flops, e0, e1, 0.0))
-
-
-class _SideWgrad:
-    """Weight gradients on a second HIP stream.  They are leaves of the backward pass: nothing on the main chain reads a dW before the optimizer, and the dense
-    data-gradient launches they sit between run one block per CU (§4.4 (iii)) -- the weight-gradient blocks of the other queue share those CUs.  Every launch is
-    ordered behind an event of the main stream (its operands are complete) and the main stream joins once at the end of the backward pass.
-
-    Operand lifetime (round 6): the operands of the last ``LAG`` side launches are kept alive HERE, and before the launch that pushes one out of that window
-    the main stream waits for its completion event -- so an operand returns to the main stream's allocator pool only behind a stream-ordered wait, and the next
-    main-stream kernel that is handed the same block cannot overtake the side launch still reading it.  Rounds 3-5 used ``Tensor.record_stream`` instead: the
-    caching allocator then parks every freed operand until an event recorded AT FREE TIME on the side stream has completed, and with the host a whole iteration
-    ahead of the device no block ever became reusable -- the pool of the adversarial iteration grew to 113 GB for 29 GB of live tensors, with GB-sized
-    ``hipMalloc``s inside the first dozen iterations (the 1 431 ms "adversarial" record of round 5: one warm-up + three timed iterations, all of them allocating)."""
-
-    try:
-        LAG = max(1, int(os.environ.get("SA_SIDE_WGRAD_LAG", "3")))
-    except ValueError:
-        raise ValueError(f"SA_SIDE_WGRAD_LAG={os.environ.get('SA_SIDE_WGRAD_LAG')!r}: expected the number of side-stream launches whose operands stay alive (an integer >= 1)") from None
-
-    def __init__(self, dev):
-        self.main = torch.cuda.current_stream(dev)
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
-        if key not in _SIDE_STREAMS:
-            _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
-        self.side = _SIDE_STREAMS[key]
-        self.inflight = collections.deque()
-
-    def run(self, fn, *operands):
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        self.side.wait_event(ev)
-        with torch.cuda.stream(self.side):
-            fn()                                  # (workspaces allocated in here come from the side stream's own pool: stream-ordered reuse)
-            done = torch.cuda.Event()
-            done.record(self.side)
-        self.inflight.append((done, operands))
-        while len(self.inflight) > self.LAG:
-            old, ops = self.inflight.popleft()
-            self.main.wait_event(old)
-            del ops
-
-    def join(self):
-        self.main.wait_stream(self.side)
-        self.inflight.clear()
-
-
-class _GradCtx:
-    def __init__(self, sink=None, side=None):
-        self.sink, self.grads, self.side = sink, {}, side
-
-    def wgrad(self, op, x, g, dw, db):
-        """op.wgrad(x, g, dw, db), on the side stream when there is one"""
-        if self.side is None:
-            op.wgrad(x, g, dw, db)
-        else:
-            self.side.run(lambda: op.wgrad(x, g, dw, db), x, g, dw, db)
-
-    def buf(self, p):
-        if p is None:
-            return None
-        if self.sink is not None:
-            b = self.sink.buffer(p)
-            if b is not None:
-                return b
-        t = self.grads.get(p)
-        if t is None:
-            t = torch.zeros_like(p)
-            self.grads[p] = t
-        return t
-
-    def done(self, *params):
-        if self.sink is None:
-            return
-        if self.side is not None and getattr(self.sink, "active", True):
-            # DDP: a bucket's all-reduce is ordered behind an event of the CURRENT stream (runtime/ddp.GradReducer._launch); the gradients of these parameters
-            # were queued on the main stream (bias / gate gradients) and on the weight-gradient stream, so report them from the latter after it has caught up
-            self.side.side.wait_stream(self.side.main)
-            with torch.cuda.stream(self.side.side):
-                self._report(params)
-            return
-        self._report(params)
-
-    def _report(self, params):
-        params = [p for p in params if p is not None]
-        if hasattr(self.sink, "flush"):
-            tok = self.sink.flush()       # optimizer slices deferred by EARLIER reports: everything that reads their parameters is queued (runtime/ddp.GradReducer.flush)
-            for p in params:
-                self.sink.ready(p, tok)
-        else:
-            for p in params:
-                self.sink.ready(p)
 
 
 class _LayerEngine:
@@ -442,16 +339,12 @@ class _LayerEngine:
         assert N <= tab.shape[0] and tab.shape[1] == self.dh and tab.is_contiguous()
         R, inner = B * N, self.H * self.dh
         if k.data_ptr() - q.data_ptr() == inner * 4 and q.stride(0) == k.stride(0):   # column blocks of one matrix: one launch
-            _ck(lib.sa_rotary_pairs(_ffi.ptr(q), q.stride(0), 0, self.G, self.dh, _ffi.ptr(tab), _ffi.ptr(q), q.stride(0), 0, N, R, transpose, 2, inner, inner, st),
+            _ffi.check(lib.sa_rotary_pairs(_ffi.ptr(q), q.stride(0), 0, self.G, self.dh, _ffi.ptr(tab), _ffi.ptr(q), q.stride(0), 0, N, R, transpose, 2, inner, inner, st),
                 "sa_rotary_pairs(q|k)")
         else:
             for t in (q, k):
-                _ck(lib.sa_rotary_pairs(_ffi.ptr(t), t.stride(0), 0, self.G, self.dh, _ffi.ptr(tab), _ffi.ptr(t), t.stride(0), 0, N, R, transpose, 1, 0, 0, st),
+                _ffi.check(lib.sa_rotary_pairs(_ffi.ptr(t), t.stride(0), 0, self.G, self.dh, _ffi.ptr(tab), _ffi.ptr(t), t.stride(0), 0, N, R, transpose, 1, 0, 0, st),
                     "sa_rotary_pairs")
-
-    def invalidate(self):
-        for op in self.ops.values():
-            op.invalidate()
 
     @staticmethod
     def _stacked(ts):
@@ -506,7 +399,7 @@ class _LayerEngine:
         ver, ps = self._pop[0], self._pop[2]
         if self._ptiles is None or self._ptiles[0] != ver:
             tiles = torch.empty(5 * 16384, dtype=torch.uint8, device=ps.device)
-            _ck(_ffi.lib().sa_favor_fused_proj_tiles(_ffi.ptr(ps), self.m, _ffi.ptr(tiles), _ffi.stream()), "sa_favor_fused_proj_tiles")
+            _ffi.check(_ffi.lib().sa_favor_fused_proj_tiles(_ffi.ptr(ps), self.m, _ffi.ptr(tiles), _ffi.stream()), "sa_favor_fused_proj_tiles")
             self._ptiles = (ver, tiles)
         return self._ptiles[1], ps
 
@@ -543,7 +436,7 @@ class _LayerEngine:
         lib, st = _ffi.lib(), _ffi.stream()
         y = torch.empty_like(x)
         stats = torch.empty(2 * R, dtype=torch.float32, device=x.device)
-        _ck(lib.sa_layernorm_fwd(_ffi.ptr(x), _ffi.ptr(wrap.norm.weight), _ffi.ptr(wrap.norm.bias), _ffi.ptr(y), None, 0, _ffi.ptr(stats), R, self.dim,
+        _ffi.check(lib.sa_layernorm_fwd(_ffi.ptr(x), _ffi.ptr(wrap.norm.weight), _ffi.ptr(wrap.norm.bias), _ffi.ptr(y), None, 0, _ffi.ptr(stats), R, self.dim,
                                  wrap.norm.eps, st), "sa_layernorm_fwd")
         return y, stats
 
@@ -589,10 +482,10 @@ class _LayerEngine:
         if L > 0 and la_args is None:
             qr, kr, lse = sv["qr"], sv["kr"], sv["lse"]
             if pa:
-                _ck(lib.sa_local_attn_fwd_dropout(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh,
+                _ffi.check(lib.sa_local_attn_fwd_dropout(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh,
                                                   _ffi.ptr(lse), B, N, L, self.W, dh, _ffi.ptr(attn_lp), pa, seed, self.site + 2, st), "sa_local_attn_fwd_dropout")
             else:
-                _ck(lib.sa_local_attn_fwd(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh, _ffi.ptr(lse),
+                _ffi.check(lib.sa_local_attn_fwd(_ffi.ptr(qr), L * dh, 0, _ffi.ptr(kr), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), inner, G * dh, _ffi.ptr(lse),
                                           B, N, L, self.W, dh, _ffi.ptr(attn_lp), st), "sa_local_attn_fwd")
         attnT = attn_lp if attn_lp is not None else _cast(attn, T)
         ga = self._gate(self.aw, dev)
@@ -601,7 +494,7 @@ class _LayerEngine:
             Fa = self.ops["to_out"].fprop(_as5(attnT)).view(R, self.dim)
             x1 = torch.empty_like(x)
             x1T = torch.empty(x.shape, dtype=T, device=dev) if lp else None
-            _ck(lib.sa_dropout_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), _ffi.ptr(x1T), _ffi.dtype_id(T) if lp else 0,
+            _ffi.check(lib.sa_dropout_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), _ffi.ptr(x1T), _ffi.dtype_id(T) if lp else 0,
                                           x.numel(), pa, seed, self.site + 1, st), "sa_dropout_rezero_fwd")
         elif lp:
             # throughput mode: x1 = x + g F leaves the to_out launch itself (fp32 residual stream + its bf16 copy for the next dense layer + the branch
@@ -611,7 +504,7 @@ class _LayerEngine:
         else:       # LayerNorm / fp32: the residual as a launch of its own, no low-precision copy
             Fa = self.ops["to_out"].fprop(_as5(attnT)).view(R, self.dim)
             x1, x1T = torch.empty_like(x), None
-            _ck(lib.sa_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), None, 0, x.numel(), st), "sa_rezero_fwd")
+            _ffi.check(lib.sa_rezero_fwd(_ffi.ptr(x), _ffi.ptr(Fa), _ffi.dtype_id(Fa.dtype), _ffi.ptr(ga), _ffi.ptr(x1), None, 0, x.numel(), st), "sa_rezero_fwd")
         gf = self._gate(self.fw, dev)
         xf, st_f = self._pre(self.fw, x1, R)
         xfT = x1T if lp else _cast(xf, T)
@@ -620,18 +513,18 @@ class _LayerEngine:
             h, u, _ = self.ops["w1"].fprop(_as5(xfT), act=_ffi.ACT_GELU, want_pre=True)
             h, u = h.view(R, -1), u.view(R, -1)
             if pf:   # ff_dropout: h *= keep / (1 - p) in place, between the GELU and w2 (u stays the undropped pre-activation)
-                _ck(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
+                _ffi.check(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
             x2, Ff, x2T = self.ops["w2"].fprop(_as5(h), out_dtype=f32, alpha=gf, addend=_as5(x1), want_pre=True, want_lp=True)
             x2, Ff, self.out_lp = x2.view(R, self.dim), Ff.view(R, self.dim), x2T.view(R, self.dim)
         else:       # LayerNorm / fp32: GELU and the residual as launches of their own
             u = self.ops["w1"].fprop(_as5(xfT)).view(R, -1)
             h = torch.empty_like(u)
-            _ck(lib.sa_gelu(_ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(h), _ffi.dtype_id(h.dtype), u.numel(), st), "sa_gelu")
+            _ffi.check(lib.sa_gelu(_ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(h), _ffi.dtype_id(h.dtype), u.numel(), st), "sa_gelu")
             if pf:
-                _ck(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
+                _ffi.check(lib.sa_dropout_apply(_ffi.ptr(h), _ffi.dtype_id(h.dtype), h.numel(), pf, seed, self.site, st), "sa_dropout_apply")
             Ff = self.ops["w2"].fprop(_as5(h)).view(R, self.dim)
             x2, self.out_lp = torch.empty_like(x), None
-            _ck(lib.sa_rezero_fwd(_ffi.ptr(x1), _ffi.ptr(Ff), _ffi.dtype_id(Ff.dtype), _ffi.ptr(gf), _ffi.ptr(x2), None, 0, x.numel(), st), "sa_rezero_fwd")
+            _ffi.check(lib.sa_rezero_fwd(_ffi.ptr(x1), _ffi.ptr(Ff), _ffi.dtype_id(Ff.dtype), _ffi.ptr(gf), _ffi.ptr(x2), None, 0, x.numel(), st), "sa_rezero_fwd")
         if tape is not None:
             sv.update(attnT=attnT, Fa=Fa, x1=x1, xf=xf, xfT=xfT, st_f=st_f, u=u, h=h, Ff=Ff)
             tape.append(sv)
@@ -658,13 +551,13 @@ class _LayerEngine:
                                           _ffi.ptr(attn), inner, _ffi.ptr(inv), 1e-6, B, N, G, m, _ffi.ptr(state), _ffi.ptr(attn_lp),
                                           ctypes.byref(la) if la is not None else None, st)
         t0 = _favor_bracket_begin()
-        _ck(lib.sa_favor_fused_prepass(_ffi.ptr(q), _ffi.ptr(k), qs, G, _ffi.ptr(tiles), _ffi.ptr(offq), _ffi.ptr(amq), _ffi.ptr(offk), _ffi.ptr(gws), R * G, m, dh, st),
+        _ffi.check(lib.sa_favor_fused_prepass(_ffi.ptr(q), _ffi.ptr(k), qs, G, _ffi.ptr(tiles), _ffi.ptr(offq), _ffi.ptr(amq), _ffi.ptr(offk), _ffi.ptr(gws), R * G, m, dh, st),
             "sa_favor_fused_prepass")
         rc = favor_fwd(la_args)
         if rc == _ffi.SA_EUNSUPPORTED and la_args is not None:      # (exact-fp32 local attention: its kernels cannot share the launch) -> separate launches
             la_args = None
             rc = favor_fwd(None)
-        _ck(rc, "sa_favor_fused_fwd")
+        _ffi.check(rc, "sa_favor_fused_fwd")
         _favor_bracket_end(t0, "favor_prepass+fstates+fout_a" + ("_la" if la_args is not None else ""), B * N * G * FAVOR_FWD_FLOP_PER_HEAD_ROW(m, dh))
         sv.update(fused=True, offq=offq, offk=offk, amq=amq, gws=gws, inv=inv, scan_state=state if tape is not None else None)
         return la_args
@@ -690,18 +583,18 @@ class _LayerEngine:
         kmode = 0      # the keys' feature map finds the global maximum itself ...
         if not self._xf:
             # queries: projection and feature map in one launch (the row maximum is local to the block)
-            _ck(lib.sa_favor_project_features(_ffi.ptr(q), qs, G, _ffi.ptr(ps), _ffi.ptr(ddq), _ffi.ptr(qf), R * G, m, LDF, dh, st), "sa_favor_project_features(q)")
-            _ck(lib.sa_favor_project(_ffi.ptr(k), qs, G, _ffi.ptr(ps), _ffi.ptr(ddk), _ffi.ptr(gws), R * G, m, LDF, dh, st), "sa_favor_project(k)")
+            _ffi.check(lib.sa_favor_project_features(_ffi.ptr(q), qs, G, _ffi.ptr(ps), _ffi.ptr(ddq), _ffi.ptr(qf), R * G, m, LDF, dh, st), "sa_favor_project_features(q)")
+            _ffi.check(lib.sa_favor_project(_ffi.ptr(k), qs, G, _ffi.ptr(ps), _ffi.ptr(ddk), _ffi.ptr(gws), R * G, m, LDF, dh, st), "sa_favor_project(k)")
             kmode = 2  # ... unless the projection kernel already left it in gws (from its accumulators: no extra pass over ddk)
         else:
-            _ck(lib.sa_favor_features_fwd(_ffi.ptr(ddq), _ffi.ptr(qg), sst, 0, G, dh, 1, _ffi.ptr(qf), None, R * G, m, LDF, st), "favor_features(q)")
-        _ck(lib.sa_favor_features_fwd(_ffi.ptr(ddk), _ffi.ptr(kg), sst, 0, G, dh, kmode, _ffi.ptr(kf), _ffi.ptr(gws), R * G, m, LDF, st), "favor_features(k)")
+            _ffi.check(lib.sa_favor_features_fwd(_ffi.ptr(ddq), _ffi.ptr(qg), sst, 0, G, dh, 1, _ffi.ptr(qf), None, R * G, m, LDF, st), "favor_features(q)")
+        _ffi.check(lib.sa_favor_features_fwd(_ffi.ptr(ddk), _ffi.ptr(kg), sst, 0, G, dh, kmode, _ffi.ptr(kf), _ffi.ptr(gws), R * G, m, LDF, st), "favor_features(k)")
         ws = self._scan_ws(B, N, G, dev)
         if tape is not None:   # training: the chunk states (sum k' (x) v, sum k') are kept for the dq' scan of the backward pass
             ws = torch.empty_like(ws)
         inv = torch.empty(R * G, dtype=f32, device=dev)
         # the running key sums ride along as an extra state column of the scan, which divides by the normaliser itself
-        _ck(lib.sa_favor_scan_a_norm(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dh,
+        _ffi.check(lib.sa_favor_scan_a_norm(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dh,
                                      _ffi.ptr(ws), self._xf, st), "sa_favor_scan_a_norm")
         sv.update(qg=qg, kg=kg, ddq=ddq, ddk=ddk, qf=qf, kf=kf, gws=gws, inv=inv, scan_state=ws if tape is not None else None)
 
@@ -716,11 +609,11 @@ class _LayerEngine:
         qkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
         qr, kr = qkr[0], qkr[1]
         if k.data_ptr() - q.data_ptr() == inner * 4 and q.stride(0) == k.stride(0):   # q | k are column blocks of one matrix: one launch rotates both
-            _ck(lib.sa_rotary_groups(_ffi.ptr(q), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(qkr), L * dh, 0, N, R, 0, 0, 2, inner, R * L * dh, None, st),
+            _ffi.check(lib.sa_rotary_groups(_ffi.ptr(q), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(qkr), L * dh, 0, N, R, 0, 0, 2, inner, R * L * dh, None, st),
                 "sa_rotary_groups(q|k)")
         else:
-            _ck(lib.sa_rotary(_ffi.ptr(q), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(qr), L * dh, 0, N, R, 0, 0, st), "sa_rotary(q)")
-            _ck(lib.sa_rotary(_ffi.ptr(k), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(kr), L * dh, 0, N, R, 0, 0, st), "sa_rotary(k)")
+            _ffi.check(lib.sa_rotary(_ffi.ptr(q), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(qr), L * dh, 0, N, R, 0, 0, st), "sa_rotary(q)")
+            _ffi.check(lib.sa_rotary(_ffi.ptr(k), qs, G * dh, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(kr), L * dh, 0, N, R, 0, 0, st), "sa_rotary(k)")
         lse = torch.empty(R * L, dtype=f32, device=dev)
         sv.update(qr=qr, kr=kr, lse=lse)
         a = self._local_args(sv, v, qs)
@@ -777,7 +670,7 @@ class _LayerEngine:
         wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in ws])
         bp = (ctypes.c_void_p * n)(*[(m.bias.data_ptr() if m.bias is not None else None) for m in mods])
         so = (ctypes.c_int32 * n)(*[m.weight.shape[0] for m in mods])
-        _ck(lib.sa_gemv_rows(_ffi.ptr(x), x.stride(0), cin, B, n, wp, bp, so, _ffi.ptr(y), y.stride(0), act, _ffi.ptr(res) if res is not None else None,
+        _ffi.check(lib.sa_gemv_rows(_ffi.ptr(x), x.stride(0), cin, B, n, wp, bp, so, _ffi.ptr(y), y.stride(0), act, _ffi.ptr(res) if res is not None else None,
                              res.stride(0) if res is not None else 0, _ffi.ptr(gate), rnd, rw, 1 if (round_out and rnd) else 0, st), "sa_gemv_rows")
         return y
 
@@ -808,18 +701,18 @@ class _LayerEngine:
             # both kinds of heads in TWO launches: [projections | local heads over four key segments], [FAVOR+ update | combine of the segments]
             self._proj_op()
             cosb, sinb = self._rot_tables(N, dev)
-            _ck(lib.sa_attn_step(_ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(self._pop[2]), B, G, L, dh, m, LDF, _ffi.ptr(stt["smax"]), _ffi.ptr(stt["kmax"]),
+            _ffi.check(lib.sa_attn_step(_ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(self._pop[2]), B, G, L, dh, m, LDF, _ffi.ptr(stt["smax"]), _ffi.ptr(stt["kmax"]),
                                  _ffi.ptr(stt["dd"]), _ffi.ptr(stt["E"]), _ffi.ptr(stt["Ez"]), _ffi.ptr(stt["V1"]), _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(stt["kc"]),
                                  _ffi.ptr(stt["vc"]), N, self.W, _ffi.ptr(stt["lpart"]), _ffi.ptr(pos), _ffi.ptr(attn), inner, st), "sa_attn_step")
         if G > 0 and not merged:
             self._proj_op()
             ps = self._pop[2]    # projection matrix with the data normaliser folded in
-            _ck(lib.sa_favor_step(_ffi.ptr(qkv), 3 * inner, 0, _ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(qkv), 3 * inner, 2 * inner, _ffi.ptr(ps), B, G, dh, m, LDF,
+            _ffi.check(lib.sa_favor_step(_ffi.ptr(qkv), 3 * inner, 0, _ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(qkv), 3 * inner, 2 * inner, _ffi.ptr(ps), B, G, dh, m, LDF,
                                   _ffi.ptr(stt["smax"]), _ffi.ptr(stt["kmax"]), _ffi.ptr(stt["dd"]), _ffi.ptr(stt["E"]), _ffi.ptr(stt["Ez"]), _ffi.ptr(stt["V1"]),
                                   _ffi.ptr(pos), _ffi.ptr(attn), inner, 0, st), "sa_favor_step")
         if L > 0 and not merged:
             cosb, sinb = self._rot_tables(N, dev)
-            _ck(lib.sa_local_attn_step(_ffi.ptr(qkv), 3 * inner, G * dh, _ffi.ptr(qkv), 3 * inner, inner + G * dh, _ffi.ptr(qkv), 3 * inner, 2 * inner + G * dh,
+            _ffi.check(lib.sa_local_attn_step(_ffi.ptr(qkv), 3 * inner, G * dh, _ffi.ptr(qkv), 3 * inner, inner + G * dh, _ffi.ptr(qkv), 3 * inner, 2 * inner + G * dh,
                                        _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(stt["kc"]), _ffi.ptr(stt["vc"]), _ffi.ptr(pos), B, N, L, self.W, dh, _ffi.ptr(attn),
                                        inner, G * dh, st), "sa_local_attn_step")
         x1 = torch.empty_like(x)
@@ -843,22 +736,22 @@ class _LayerEngine:
             p, seed, site = drop
             det = self.rezero and debug.deterministic()
             scratch = torch.zeros(1 + 1024, dtype=torch.float32, device=dev) if det else None
-            _ck(lib.sa_dropout_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype),
+            _ffi.check(lib.sa_dropout_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype),
                                           _ffi.ptr(scratch if det else dg), dy.numel(), p, seed, site, st), "sa_dropout_rezero_bwd")
             if det:    # d g = <dy, F'> in a fixed order, as below
-                _ck(lib.sa_dot_det(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), dy.numel(), _ffi.ptr(dg), 1, _ffi.ptr(scratch[1:]), st), "sa_dot_det")
+                _ffi.check(lib.sa_dot_det(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), dy.numel(), _ffi.ptr(dg), 1, _ffi.ptr(scratch[1:]), st), "sa_dot_det")
             if self.rezero:
                 gc.done(wrap.g)
             return dF
         if self.rezero and debug.deterministic():
             # --deterministic: d g = <dy, F> in a fixed order (sa_dot_det) instead of one atomic per block; the elementwise half of the kernel runs as usual
             scratch = torch.zeros(1 + 1024, dtype=torch.float32, device=dev)
-            _ck(lib.sa_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype), _ffi.ptr(scratch),
+            _ffi.check(lib.sa_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype), _ffi.ptr(scratch),
                                   dy.numel(), st), "sa_rezero_bwd")
-            _ck(lib.sa_dot_det(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), dy.numel(), _ffi.ptr(dg), 1, _ffi.ptr(scratch[1:]), st), "sa_dot_det")
+            _ffi.check(lib.sa_dot_det(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), dy.numel(), _ffi.ptr(dg), 1, _ffi.ptr(scratch[1:]), st), "sa_dot_det")
             gc.done(wrap.g)
             return dF
-        _ck(lib.sa_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype), _ffi.ptr(dg),
+        _ffi.check(lib.sa_rezero_bwd(_ffi.ptr(dy), _ffi.ptr(Fout), _ffi.dtype_id(Fout.dtype), _ffi.ptr(g), _ffi.ptr(dF), _ffi.dtype_id(dF.dtype), _ffi.ptr(dg),
                               dy.numel(), st), "sa_rezero_bwd")
         if self.rezero:
             gc.done(wrap.g)
@@ -873,17 +766,17 @@ class _LayerEngine:
         if debug.deterministic():   # the weight / bias gradients as fixed-order column sums (see _LayerNormFn.backward)
             from ...engine import colsum_det
             junk = torch.zeros(2, self.dim, dtype=torch.float32, device=dres.device)
-            _ck(lib.sa_layernorm_bwd(_ffi.ptr(dxin), _ffi.ptr(xres), _ffi.ptr(wrap.norm.weight), _ffi.ptr(stats), _ffi.ptr(dx), _ffi.ptr(junk[0]), _ffi.ptr(junk[1]), R,
+            _ffi.check(lib.sa_layernorm_bwd(_ffi.ptr(dxin), _ffi.ptr(xres), _ffi.ptr(wrap.norm.weight), _ffi.ptr(stats), _ffi.ptr(dx), _ffi.ptr(junk[0]), _ffi.ptr(junk[1]), R,
                                      self.dim, st), "sa_layernorm_bwd")
             prod = torch.empty_like(dxin)
-            _ck(lib.sa_layernorm_dwprod(_ffi.ptr(dxin), _ffi.ptr(xres), _ffi.ptr(stats), _ffi.ptr(prod), R, self.dim, st), "sa_layernorm_dwprod")
+            _ffi.check(lib.sa_layernorm_dwprod(_ffi.ptr(dxin), _ffi.ptr(xres), _ffi.ptr(stats), _ffi.ptr(prod), R, self.dim, st), "sa_layernorm_dwprod")
             colsum_det(prod.view(R, self.dim), self.dim, gc.buf(wrap.norm.weight))
             colsum_det(dxin.view(R, self.dim), self.dim, gc.buf(wrap.norm.bias))
         else:
-            _ck(lib.sa_layernorm_bwd(_ffi.ptr(dxin), _ffi.ptr(xres), _ffi.ptr(wrap.norm.weight), _ffi.ptr(stats), _ffi.ptr(dx), _ffi.ptr(gc.buf(wrap.norm.weight)),
+            _ffi.check(lib.sa_layernorm_bwd(_ffi.ptr(dxin), _ffi.ptr(xres), _ffi.ptr(wrap.norm.weight), _ffi.ptr(stats), _ffi.ptr(dx), _ffi.ptr(gc.buf(wrap.norm.weight)),
                                      _ffi.ptr(gc.buf(wrap.norm.bias)), R, self.dim, st), "sa_layernorm_bwd")
         gc.done(wrap.norm.weight, wrap.norm.bias)
-        _ck(lib.sa_axpy(_ffi.ptr(dx), _ffi.ptr(dres), 1.0, dx.numel(), st), "sa_axpy")
+        _ffi.check(lib.sa_axpy(_ffi.ptr(dx), _ffi.ptr(dres), 1.0, dx.numel(), st), "sa_axpy")
         return dx
 
     def _favor_fused_bwd(self, sv, dattn, dq, dk, dv, dq_lp, dk_lp, dv_lp, B, N, pa):
@@ -919,7 +812,7 @@ class _LayerEngine:
         if rc == _ffi.SA_EUNSUPPORTED and la_args is not None:   # exact-fp32 local attention / unpaired launches: separate launches in the caller
             la_args = dqkr = None
             rc = favor_bwd(None)
-        _ck(rc, "sa_favor_fused_bwd")
+        _ffi.check(rc, "sa_favor_fused_bwd")
         _favor_bracket_end(t0, "favor_fdden+fpair_states_b+fpair_b_a+fkey_fix" + ("_la" if la_args is not None else ""),
                            2.0 * B * N * G * FAVOR_FWD_FLOP_PER_HEAD_ROW(m, dh))
         sv["scan_state"] = None
@@ -933,18 +826,18 @@ class _LayerEngine:
         v, attn, qf, kf, inv = sv["v"], sv["attn"], sv["qf"], sv["kf"], sv["inv"]
         qs = dq.stride(0)
         dden = torch.empty(R * G, dtype=f32, device=dev)
-        _ck(lib.sa_favor_dden(_ffi.ptr(dattn), _ffi.ptr(attn), inner, 0, G, dh, _ffi.ptr(inv), _ffi.ptr(dden), R * G, st), "sa_favor_dden")
+        _ffi.check(lib.sa_favor_dden(_ffi.ptr(dattn), _ffi.ptr(attn), inner, 0, G, dh, _ffi.ptr(inv), _ffi.ptr(dden), R * G, st), "sa_favor_dden")
         ws = self._scan_ws(B, N, G, dev)
         dqf, dkf = torch.empty_like(qf), torch.empty_like(kf)
         kept = sv.get("scan_state")   # the forward's chunk states: same (a = k', b = v) -> no state / prefix passes for dq'
-        _ck(lib.sa_favor_scan_b_cum(_ffi.ptr(kf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dqf), _ffi.ptr(dden), 1, 1e-6,
+        _ffi.check(lib.sa_favor_scan_b_cum(_ffi.ptr(kf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dqf), _ffi.ptr(dden), 1, 1e-6,
                                     B, N, G, LDF, dh, 0, _ffi.ptr(kept if kept is not None else ws), (1 if kept is not None else 0) | self._xf, st),
             "sa_favor_scan_b_cum(dq')")
         sv["scan_state"] = None
-        _ck(lib.sa_favor_scan_b_cum(_ffi.ptr(qf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dkf), _ffi.ptr(dden), 2, 0.0,
+        _ffi.check(lib.sa_favor_scan_b_cum(_ffi.ptr(qf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dkf), _ffi.ptr(dden), 2, 0.0,
                                     B, N, G, LDF, dh, 1, _ffi.ptr(ws), self._xf, st), "sa_favor_scan_b_cum(dk')")
         # dv runs on the states the dk' scan just built (same a = q', b = d attn * inv, reversed)
-        _ck(lib.sa_favor_scan_a_state(_ffi.ptr(qf), _ffi.ptr(kf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dv), qs, 0, None, B, N, G, LDF, dh, 1, 0,
+        _ffi.check(lib.sa_favor_scan_a_state(_ffi.ptr(qf), _ffi.ptr(kf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dv), qs, 0, None, B, N, G, LDF, dh, 1, 0,
                                       _ffi.ptr(ws), 3 | self._xf, st), "sa_favor_scan_a_state(dv)")
         pop = self._proj_op()
         tsum = torch.empty(R * G, dtype=f32, device=dev)
@@ -952,9 +845,9 @@ class _LayerEngine:
             dddq, dddk = torch.empty_like(qf), torch.empty_like(kf)
             dqg = torch.empty(R, G * dh, dtype=f32, device=dev)
             dkg = torch.empty(R, G * dh, dtype=f32, device=dev)
-            _ck(lib.sa_favor_features_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), G * dh, 0, G, dh, 1, _ffi.ptr(dddq), _ffi.ptr(dqg),
+            _ffi.check(lib.sa_favor_features_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), G * dh, 0, G, dh, 1, _ffi.ptr(dddq), _ffi.ptr(dqg),
                                           None, None, R * G, m, LDF, st), "favor_features_bwd(q)")
-            _ck(lib.sa_favor_features_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), G * dh, 0, G, dh, 0, _ffi.ptr(dddk), _ffi.ptr(dkg),
+            _ffi.check(lib.sa_favor_features_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), G * dh, 0, G, dh, 0, _ffi.ptr(dddk), _ffi.ptr(dkg),
                                           _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, st), "favor_features_bwd(k)")
             rg = (1, 1, R * G)
             dqg = pop.dgrad(dddq.view(1, 1, 1, R * G, LDF), rg, addend=dqg.view(1, 1, 1, R * G, dh), fwd_out_stride=LDF).view(R, G * dh)
@@ -963,12 +856,12 @@ class _LayerEngine:
             dk[:, : G * dh] = dkg
         else:          # throughput mode: one launch per side straight into the global-head columns of dq / dk (d loss / d dd never exists)
             ps = self._pop[2]
-            _ck(lib.sa_favor_features_project_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), qs, G, _ffi.ptr(ps), 1, _ffi.ptr(dq),
+            _ffi.check(lib.sa_favor_features_project_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(sv["ddq"]), _ffi.ptr(sv["qg"]), qs, G, _ffi.ptr(ps), 1, _ffi.ptr(dq),
                                                   None, None, R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(q)")
-            _ck(lib.sa_favor_features_project_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), qs, G, _ffi.ptr(ps), 0, _ffi.ptr(dk),
+            _ffi.check(lib.sa_favor_features_project_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), qs, G, _ffi.ptr(ps), 0, _ffi.ptr(dk),
                                                   _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(k)")
 
-    def bwd(self, dx2, sv, B, N, gc: _GradCtx):
+    def bwd(self, dx2, sv, B, N, gc: GradCtx):
         self._sync()
         lib, st, dev, T = _ffi.lib(), _ffi.stream(), dx2.device, self.dtype
         R, H, G, L, dh = B * N, self.H, self.G, self.L, self.dh
@@ -987,7 +880,7 @@ class _LayerEngine:
             u = sv["u"]
             assert dh_.shape[-1] == u.shape[-1] and dh_.numel() == u.numel()
             du = torch.empty_like(dh_)
-            _ck(lib.sa_dropout_gelu_bwd(_ffi.ptr(dh_), _ffi.dtype_id(dh_.dtype), _ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(du), _ffi.dtype_id(du.dtype), u.numel(),
+            _ffi.check(lib.sa_dropout_gelu_bwd(_ffi.ptr(dh_), _ffi.dtype_id(dh_.dtype), _ffi.ptr(u), _ffi.dtype_id(u.dtype), _ffi.ptr(du), _ffi.dtype_id(du.dtype), u.numel(),
                                         pf, seed, self.site, st), "sa_dropout_gelu_bwd")
             del dh_
         else:
@@ -1030,19 +923,19 @@ class _LayerEngine:
                 dqkr = torch.empty(2, R, L * dh, dtype=f32, device=dev)
                 Db = torch.empty(R * L, dtype=f32, device=dev)
                 if pa:
-                    _ck(lib.sa_local_attn_bwd_dropout(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
+                    _ffi.check(lib.sa_local_attn_bwd_dropout(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
                                                       inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W,
                                                       dh, _ffi.ptr(dv_lp), pa, seed, self.site + 2, st), "sa_local_attn_bwd_dropout")
                 else:
-                    _ck(lib.sa_local_attn_bwd(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
+                    _ffi.check(lib.sa_local_attn_bwd(_ffi.ptr(sv["qr"]), L * dh, 0, _ffi.ptr(sv["kr"]), L * dh, 0, _ffi.ptr(v), qs, G * dh, _ffi.ptr(attn), _ffi.ptr(dattn),
                                               inner, G * dh, _ffi.ptr(sv["lse"]), _ffi.ptr(dqkr[0]), _ffi.ptr(dqkr[1]), _ffi.ptr(dv), _ffi.ptr(Db), B, N, L, self.W, dh,
                                               _ffi.ptr(dv_lp), st), "sa_local_attn_bwd")
             if fused_qkv:   # dq | dk are column blocks of one matrix: one launch
-                _ck(lib.sa_rotary_groups(_ffi.ptr(dqkr), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, 2, R * L * dh, inner, _ffi.ptr(dq_lp), st),
+                _ffi.check(lib.sa_rotary_groups(_ffi.ptr(dqkr), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, 2, R * L * dh, inner, _ffi.ptr(dq_lp), st),
                     "sa_rotary_groups^T(q|k)")
             else:
-                _ck(lib.sa_rotary(_ffi.ptr(dqkr[0]), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(q)")
-                _ck(lib.sa_rotary(_ffi.ptr(dqkr[1]), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dk), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(k)")
+                _ffi.check(lib.sa_rotary(_ffi.ptr(dqkr[0]), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dq), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(q)")
+                _ffi.check(lib.sa_rotary(_ffi.ptr(dqkr[1]), L * dh, 0, L, dh, _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(dk), qs, G * dh, N, R, 1, 0, st), "sa_rotary^T(k)")
         self._rotate_global(dq, dk, B, N, 1)
         xaT = _as5(sv["xaT"])
         base = _as5(dx1) if self.rezero else None
@@ -1081,9 +974,8 @@ class _StackChain:
     def params(self):
         return [p for p in self.base.parameters()]
 
-    def invalidate(self):
-        for l in self.layers:
-            l.invalidate()
+    def ops(self):
+        return [op for l in self.layers for op in l.ops.values()]
 
     def forward(self, x, record):
         B, N, D = x.shape
@@ -1097,12 +989,9 @@ class _StackChain:
 
     def backward(self, dy, tape):
         B, N, D = dy.shape
-        # throughput mode: weight gradients on a second stream (DDP: _GradCtx.done reports a bucket's parameters from that stream)
-        side = None
-        if (self.dtype != torch.float32 and not debug.host("no_side_wgrad") and not debug.deterministic()
-                and not torch.cuda.is_current_stream_capturing()):
-            side = _SideWgrad(dy.device)
-        gc = _GradCtx(self.grad_sink, side)
+        # throughput mode: weight gradients on a second stream (DDP: GradCtx.done reports a bucket's parameters from that stream)
+        side = side_wgrad(self.dtype, dy.device, "no_side_wgrad")
+        gc = GradCtx(self.grad_sink, side)
         g = dy.reshape(B * N, D).float().contiguous()
         for l, sv in zip(reversed(self.layers), reversed(tape)):
             g = l.bwd(g, sv, B, N, gc)
@@ -1184,7 +1073,7 @@ class _EmbedFn(torch.autograd.Function):
         tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tables])
         ip = (ctypes.c_void_p * n)(*[i.data_ptr() for i in idx])
         pp = (ctypes.c_int32 * n)(*per_pos)
-        _ck(_ffi.lib().sa_embed_sum(n, tp, ip, pp, dim, N, B * N, _ffi.ptr(out), _ffi.stream()), "sa_embed_sum")
+        _ffi.check(_ffi.lib().sa_embed_sum(n, tp, ip, pp, dim, N, B * N, _ffi.ptr(out), _ffi.stream()), "sa_embed_sum")
         ctx.idx, ctx.per_pos, ctx.shapes, ctx.BN = list(idx), list(per_pos), [t.shape for t in tables], (B, N)
         return out
 
@@ -1199,9 +1088,9 @@ class _EmbedFn(torch.autograd.Function):
                 continue
             g = torch.zeros(shp, dtype=torch.float32, device=dy.device)
             if debug.deterministic():
-                _ck(_ffi.lib().sa_embed_scatter_det(_ffi.ptr(dy), _ffi.ptr(g), _ffi.ptr(ix), pp, shp[1], N, B * N, shp[0], _ffi.stream()), "sa_embed_scatter_det")
+                _ffi.check(_ffi.lib().sa_embed_scatter_det(_ffi.ptr(dy), _ffi.ptr(g), _ffi.ptr(ix), pp, shp[1], N, B * N, shp[0], _ffi.stream()), "sa_embed_scatter_det")
             else:
-                _ck(_ffi.lib().sa_embed_scatter(_ffi.ptr(dy), _ffi.ptr(g), _ffi.ptr(ix), pp, shp[1], N, B * N, _ffi.stream()), "sa_embed_scatter")
+                _ffi.check(_ffi.lib().sa_embed_scatter(_ffi.ptr(dy), _ffi.ptr(g), _ffi.ptr(ix), pp, shp[1], N, B * N, _ffi.stream()), "sa_embed_scatter")
             grads.append(g)
         return (None, None, None, None, None, *grads)
 
@@ -1215,7 +1104,7 @@ class _LayerNormFn(torch.autograd.Function):
         R, C = x2.shape
         y = torch.empty_like(x2)
         stats = torch.empty(2 * R, dtype=torch.float32, device=x.device)
-        _ck(_ffi.lib().sa_layernorm_fwd(_ffi.ptr(x2), _ffi.ptr(w), _ffi.ptr(b), _ffi.ptr(y), None, 0, _ffi.ptr(stats), R, C, eps, _ffi.stream()), "sa_layernorm_fwd")
+        _ffi.check(_ffi.lib().sa_layernorm_fwd(_ffi.ptr(x2), _ffi.ptr(w), _ffi.ptr(b), _ffi.ptr(y), None, 0, _ffi.ptr(stats), R, C, eps, _ffi.stream()), "sa_layernorm_fwd")
         ctx.save_for_backward(x2, w, stats)
         return y.view(shp)
 
@@ -1225,13 +1114,13 @@ class _LayerNormFn(torch.autograd.Function):
         R, C = x2.shape
         d = dy.reshape(R, C).float().contiguous()
         dx, dw, db = torch.empty_like(x2), torch.zeros_like(w), torch.zeros_like(w)
-        _ck(_ffi.lib().sa_layernorm_bwd(_ffi.ptr(d), _ffi.ptr(x2), _ffi.ptr(w), _ffi.ptr(stats), _ffi.ptr(dx), _ffi.ptr(dw), _ffi.ptr(db), R, C, _ffi.stream()),
+        _ffi.check(_ffi.lib().sa_layernorm_bwd(_ffi.ptr(d), _ffi.ptr(x2), _ffi.ptr(w), _ffi.ptr(stats), _ffi.ptr(dx), _ffi.ptr(dw), _ffi.ptr(db), R, C, _ffi.stream()),
             "sa_layernorm_bwd")
         if debug.deterministic():
             # --deterministic: the weight / bias gradients again as fixed-order column sums (the kernel above accumulated them with one atomic per column and block)
             from ...engine import colsum_det
             prod = torch.empty_like(x2)
-            _ck(_ffi.lib().sa_layernorm_dwprod(_ffi.ptr(d), _ffi.ptr(x2), _ffi.ptr(stats), _ffi.ptr(prod), R, C, _ffi.stream()), "sa_layernorm_dwprod")
+            _ffi.check(_ffi.lib().sa_layernorm_dwprod(_ffi.ptr(d), _ffi.ptr(x2), _ffi.ptr(stats), _ffi.ptr(prod), R, C, _ffi.stream()), "sa_layernorm_dwprod")
             dw, db = torch.zeros_like(w), torch.zeros_like(w)
             colsum_det(prod, C, dw)
             colsum_det(d, C, db)
@@ -1375,6 +1264,7 @@ class Performer(TransformerBase):
             for l in self._chain.layers:
                 l.layer_pos = self.layer_pos_emb
         self._out_op = _lin(self._out_mod(), compute_dtype)
+        self._repack = Repack(self._ops)
         self._idx_cache = {}
         self.last_dropout_seed = None      # the seed of the last training forward with ff_dropout / attn_dropout (tests replay its masks)
 
@@ -1408,19 +1298,16 @@ class Performer(TransformerBase):
                 if p.requires_grad and id(p) not in in_chain:
                     self._sink_hooks.append(p.register_post_accumulate_grad_hook(lambda q, s=sink: s.ready(q)))
 
+    def _ops(self):
+        return self._chain.ops() + [self._out_op]
+
     def invalidate_packed_weights(self):
-        self._chain.invalidate()
-        self._out_op.invalidate()
-        # every dense layer's forward / data-gradient operand again, in one launch
-        if getattr(self, "_packset", None) is None:
-            self._packset = PackSet()
-        self._packset.repack([op for l in self._chain.layers for op in l.ops.values()] + [self._out_op])
+        self._repack.all()     # every dense layer's forward / data-gradient operand again, in one launch
 
     def range_repacker(self, flat):
         """For ``FusedAdam(in_backward=reducer)``: ``opt.on_range.append(r); opt.on_step.append(r.finish)`` INSTEAD of ``invalidate_packed_weights`` --
         a layer's operands are re-packed right behind the optimizer slice of its bucket, in the shadow of the backward pass."""
-        from ...engine import RangeRepacker
-        return RangeRepacker(flat, lambda: [op for l in self._chain.layers for op in l.ops.values()] + [self._out_op])
+        return self._repack.ranges(flat)
 
     # ------------------------------------------------------------------------------------------------ sampling
     @torch.no_grad()
@@ -1506,7 +1393,7 @@ class Performer(TransformerBase):
                 p64 = pos.to(torch.int64)
                 tok.copy_(seq.gather(1, p64.expand(B, 1)).squeeze(1))
             x = torch.empty(B, dim, dtype=torch.float32, device=dev)
-            _ck(lib.sa_embed_step(n, tp, ip, pp, dim, _ffi.ptr(pos), B, _ffi.ptr(x), _ffi.stream()), "sa_embed_step")
+            _ffi.check(lib.sa_embed_step(n, tp, ip, pp, dim, _ffi.ptr(pos), B, _ffi.ptr(x), _ffi.stream()), "sa_embed_step")
             for l, stt in zip(layers, states):
                 x = l.step(x, B, npos, pos, stt)
             h = _LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps)
@@ -1515,7 +1402,7 @@ class Performer(TransformerBase):
             if fused_tail:
                 # temperature, softmax, the draw (inverse CDF against the pre-drawn uniforms -- torch.multinomial cannot be captured in a HIP graph) or arg-max,
                 # seq[:, pos + 1] (unless it belongs to the given prefix), the next step's token, pos += 1: one launch instead of ~20 small torch kernels
-                _ck(lib.sa_sample_step(_ffi.ptr(logits), B, logits.shape[1], float(temperature), _ffi.ptr(u_all), B, int(bool(sample)), int(top_k or 0), _ffi.ptr(seq),
+                _ffi.check(lib.sa_sample_step(_ffi.ptr(logits), B, logits.shape[1], float(temperature), _ffi.ptr(u_all), B, int(bool(sample)), int(top_k or 0), _ffi.ptr(seq),
                                        total, P, _ffi.ptr(pos), _ffi.ptr(ticket), _ffi.ptr(tok), _ffi.stream()), "sa_sample_step")
                 return
             logits = logits / temperature

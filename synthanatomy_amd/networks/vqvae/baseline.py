@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from ... import _ffi, conv_plan, debug
 from ..._ffi import ACT_NONE, ACT_RELU, MASK_NONE, MASK_POS
-from ...engine import ConvOp, PackSet, _launch, _ru, _tbytes, cast_pad, vec_of
+from ...engine import ConvOp, Repack, _launch, _ru, _tbytes, cast_pad, vec_of
+from ...runtime.backward import GradCtx, side_wgrad
 from .vqvae import VQVAEBase
 
 
@@ -274,6 +275,9 @@ class _ConvStage:
     def params(self):
         return [self.mod.weight, self.mod.bias]
 
+    def ops(self):
+        return [self.op]
+
     def _sync(self):
         self.op.weight, self.op.bias = self.mod.weight, self.mod.bias
 
@@ -333,6 +337,9 @@ class _Conv1Stage:
 
     def params(self):
         return [self.mod.weight, self.mod.bias]
+
+    def ops(self):
+        return [self.op, self.fallback_op]
 
     def _sync(self):
         self.op.weight, self.op.bias = self.mod.weight.view(self.mod.out_channels, self.T, 1, 1, 1), self.mod.bias
@@ -453,6 +460,9 @@ class _ConvT1Stage:
 
     def params(self):
         return [self.mod.weight, self.mod.bias]
+
+    def ops(self):
+        return [self.taps_fwd, self.taps_bwd] + ([] if self.default else [self.fallback_op])
 
     def _sync(self):
         self.taps_fwd.weight = self.taps_bwd.weight = self.mod.weight
@@ -590,6 +600,9 @@ class _SubpixelStage:
     def params(self):
         return [self.conv.weight, self.conv.bias]
 
+    def ops(self):
+        return [self.op]
+
     def _sync(self):
         self.op.weight, self.op.bias = self.conv.weight, self.conv.bias
 
@@ -628,6 +641,9 @@ class _ResStage:
 
     def params(self):
         return [self.c3m.weight, self.c3m.bias, self.c1m.weight, self.c1m.bias]
+
+    def ops(self):
+        return [self.c3, self.c1]
 
     def _sync(self):
         self.c3.weight, self.c3.bias = self.c3m.weight, self.c3m.bias
@@ -730,51 +746,6 @@ class _ResStage:
         return self.c3.dgrad(dp, dims, addend=G, mask=x if self.in_act else None, mask_mode=MASK_POS)
 
 
-class _GradCtx:
-    """Where the weight-gradient kernels accumulate.  Without a sink: fresh zeroed tensors handed back to autograd.  With a
-    sink (runtime.ddp.GradReducer): views of the flat gradient buffer, and the sink is told as soon as a parameter's
-    gradient kernels are queued so that its bucket's all-reduce can start while backward continues."""
-
-    def __init__(self, sink=None, side=None):
-        self.sink, self.grads, self.side = sink, {}, side
-
-    def wgrad(self, op, x, g, dw, db):
-        """op.wgrad(x, g, dw, db); on the second stream when there is one (networks/transformers/performer._SideWgrad: weight gradients are leaves of the pass)"""
-        if self.side is None:
-            op.wgrad(x, g, dw, db)
-        else:
-            self.side.run(lambda: op.wgrad(x, g, dw, db), x, g, dw, db)
-
-    def buf(self, p):
-        if self.sink is not None:
-            b = self.sink.buffer(p)
-            if b is not None:
-                return b
-        t = torch.zeros_like(p)
-        self.grads[p] = t
-        return t
-
-    def done(self, *params):
-        if self.sink is None:
-            return
-        if self.side is not None and getattr(self.sink, "active", True):
-            # DDP: the bucket's all-reduce waits for an event of the CURRENT stream; these gradients were queued on the main and on the weight-gradient stream
-            self.side.side.wait_stream(self.side.main)
-            with torch.cuda.stream(self.side.side):
-                self._report(params)
-            return
-        self._report(params)
-
-    def _report(self, params):
-        if hasattr(self.sink, "flush"):
-            tok = self.sink.flush()       # optimizer slices deferred by EARLIER reports: everything that reads their parameters is queued (runtime/ddp.GradReducer.flush)
-            for p in params:
-                self.sink.ready(p, tok)
-        else:
-            for p in params:
-                self.sink.ready(p)
-
-
 class _Chain:
     def __init__(self, stages, dtype, in_channels, fwd_dtype=None):
         self.stages, self.dtype, self.in_channels = stages, dtype, in_channels
@@ -785,15 +756,8 @@ class _Chain:
     def params(self) -> List[nn.Parameter]:
         return [p for s in self.stages for p in s.params()]
 
-    def ops(self):
-        return [op for s in self.stages
-                for op in (getattr(s, "op", None), getattr(s, "c3", None), getattr(s, "c1", None), getattr(s, "taps_fwd", None), getattr(s, "taps_bwd", None),
-                           getattr(s, "fallback_op", None))
-                if op is not None]
-
-    def invalidate(self):
-        for op in self.ops():
-            op.invalidate()
+    def ops(self) -> List[ConvOp]:
+        return [op for s in self.stages for op in s.ops()]
 
     def forward(self, x_ncdhw: torch.Tensor, record: bool):
         """x [B,C,D,H,W] fp32 (any strides) -> y channels-last [B,D,H,W,C'] (+ tape)."""
@@ -822,7 +786,7 @@ class _Chain:
         if self.last_tape is None:
             raise RuntimeError("last_stage_wgrad needs a recorded forward whose backward has not run yet")
         st = self.stages[-1]
-        gc = _GradCtx(None)
+        gc = GradCtx()
         if isinstance(st, (_ConvStage, _ConvT1Stage, _SubpixelStage)):
             st.bwd(G, self.last_tape[-1], gc, wgrad_only=True)   # no data gradient: the caller only wants d loss / d W_last
         else:
@@ -830,15 +794,11 @@ class _Chain:
         return gc.grads[st.params()[0]]
 
     def backward(self, G: torch.Tensor, tape):
-        side = None
         # Weight gradients are leaves of the backward pass: they run on a second HIP stream beside the data-gradient chain (round 5: default, +0.9 % on the
         # step -- 113.5 -> 112.5 ms in alternating same-box runs; overlapping launches inflate every per-kernel duration, which is why bench.py's roofline record
         # comes from a separate pass with SA_NO_SIDE_WGRAD semantics).  SA_NO_SIDE_WGRAD=1 / --deterministic: one stream.
-        if (self.dtype != torch.float32 and not debug.host("no_side_wgrad") and not debug.host("no_side_wgrad_vqvae")
-                and not debug.deterministic() and G.is_cuda):
-            from ..transformers.performer import _SideWgrad
-            side = _SideWgrad(G.device)
-        gc = _GradCtx(self.grad_sink, side)
+        side = side_wgrad(self.dtype, G.device, "no_side_wgrad", "no_side_wgrad_vqvae")
+        gc = GradCtx(self.grad_sink, side)
         for s, saved in zip(reversed(self.stages), reversed(tape)):
             G = s.bwd(G, saved, gc)
         if side is not None:
@@ -927,6 +887,7 @@ class BaselineVQVAE(VQVAEBase, nn.Module):
         self.decoder = self.construct_decoder()
         self._enc_chain = self._build_encoder_chain()
         self._dec_chain = self._build_decoder_chain()
+        self._repack = Repack(self._ops)
 
     # ---------------------------------------------------------------- parameter trees (same numbering as the reference)
     def _level_width(self, level: int, decoder: bool) -> int:
@@ -1023,18 +984,16 @@ class BaselineVQVAE(VQVAEBase, nn.Module):
         for c in self._chains():
             c.grad_sink = sink
 
+    def _ops(self) -> List[ConvOp]:
+        return [op for c in self._chains() for op in c.ops()]
+
     def invalidate_packed_weights(self):
-        """Tell the launch chains that parameters were modified through raw pointers (fused Adam kernel)."""
-        for c in self._chains():
-            c.invalidate()
-        if getattr(self, "_packset", None) is None:
-            self._packset = PackSet()
-        self._packset.repack([op for c in self._chains() for op in c.ops()])   # all packed operands again, in one launch
+        """Tell the launch chains that parameters were modified through raw pointers (fused Adam kernel): all packed operands again, in one launch."""
+        self._repack.all()
 
     def range_repacker(self, flat):
-        """For ``FusedAdam(in_backward=reducer)`` (see networks/transformers/performer.Performer.range_repacker)."""
-        from ...engine import RangeRepacker
-        return RangeRepacker(flat, lambda: [op for c in self._chains() for op in c.ops()])
+        """For ``FusedAdam(in_backward=reducer)`` (engine.Repack.ranges)."""
+        return self._repack.ranges(flat)
 
     # ---------------------------------------------------------------- accessors (baseline.py:301-327)
     def get_ema_decay(self) -> Sequence[float]:

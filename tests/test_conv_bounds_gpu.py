@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import conv_bounds as cb
+from grad_stand_in import Grads
 
 pytestmark = pytest.mark.gpu
 
@@ -338,17 +339,8 @@ def _resblock(case, gen):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- one-channel layers
-class _Grads:
-    def __init__(self, params, gen, acc):
-        self.b = {id(p): (torch.randn(p.shape, generator=gen) * 0.5 if acc else torch.zeros(p.shape)) for p in params}
-        self.init = {k: v.clone() for k, v in self.b.items()}
-        self.b = {k: v.to(DEV) for k, v in self.b.items()}
-
-    def buf(self, p):
-        return self.b[id(p)]
-
-    def done(self, *ps):
-        pass
+def _Grads(params, gen, acc):
+    return Grads(params, [torch.randn(p.shape, generator=gen) * 0.5 for p in params] if acc else None)
 
 
 def _corner_tap(w):

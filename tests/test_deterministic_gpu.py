@@ -125,7 +125,7 @@ def test_adversarial_iteration_is_bit_reproducible_in_deterministic_mode():
         flat, d_flat = FlatParams(net.parameters()), FlatParams(disc.parameters())
         opt, d_opt = FusedAdam(flat, lr=1e-3), FusedAdam(d_flat, lr=5e-4)
         opt.on_step.append(net.invalidate_packed_weights)
-        d_opt.on_step.append(lambda: [s_.op.invalidate() for s_ in disc._stages])
+        d_opt.on_step.append(disc.invalidate_packed_weights)
         tr = AdversarialTrainer(net, opt, get_generator_loss({"generator_loss": "least_square"}), MSELoss(), disc, d_opt,
                                 get_discriminator_loss({"discriminator_loss": "least_square"}), use_adversarial_adaptive_weight=True)
         with debug.override(deterministic=True):

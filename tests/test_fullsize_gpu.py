@@ -206,7 +206,7 @@ def test_adversarial_iteration_at_full_size():
     flat, d_flat = FlatParams(net.parameters()), FlatParams(disc.parameters())
     opt, d_opt = FusedAdam(flat, lr=1.65e-4), FusedAdam(d_flat, lr=5e-5)
     opt.on_step.append(net.invalidate_packed_weights)
-    d_opt.on_step.append(lambda: [s_.op.invalidate() for s_ in disc._stages])
+    d_opt.on_step.append(disc.invalidate_packed_weights)
     tr = AdversarialTrainer(net, opt, get_generator_loss({"generator_loss": "least_square"}), MSELoss(), disc, d_opt,
                             get_discriminator_loss({"discriminator_loss": "least_square"}), use_adversarial_adaptive_weight=True,
                             adaptive_adversarial_weight_threshold=0, adaptive_adversarial_weight_value=1.0)

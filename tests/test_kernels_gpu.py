@@ -9,6 +9,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from conftest import load_golden  # noqa: E402
+from grad_stand_in import Grads  # noqa: E402
 
 
 def _ops():
@@ -535,15 +536,7 @@ def test_convt1_gemm_route(dtype):
     tape = []
     out = st.fwd(xd, tape)
     _close(out[..., 0].cpu(), yr.detach()[:, 0], dtype, "convt1 fwd (gemm)")
-
-    class _G:
-        def __init__(self):
-            self.b = {id(mod.weight): torch.zeros_like(mod.weight), id(mod.bias): torch.zeros_like(mod.bias)}
-        def buf(self, p):
-            return self.b[id(p)]
-        def done(self, *ps):
-            pass
-    gr = _G()
+    gr = Grads([mod.weight, mod.bias])
     dx = st.bwd(_cl(g).cuda(), tape[0], gr)
     torch.cuda.synchronize()
     _close(dx.float().cpu(), _cl(xr.grad * (x > 0)), torch.bfloat16 if dtype == torch.bfloat16 else dtype, "convt1 dgrad (gemm)")
@@ -585,7 +578,8 @@ def test_last_layer_backward_on_the_first_layer_kernels(shape, in_act):
     """sa_convt1_backward (data gradient = conv1 forward on the gradient volume, weight gradient = conv1 weight gradient with the layer input as
     `g`, bias gradient = sum of the volume) against the im2col + GEMM route it replaces and against torch autograd on the same bf16-rounded operands."""
     from synthanatomy_amd import debug
-    from synthanatomy_amd.networks.vqvae.baseline import _ConvT1Stage, _GradCtx
+    from synthanatomy_amd.networks.vqvae.baseline import _ConvT1Stage
+    from synthanatomy_amd.runtime.backward import GradCtx
     torch.manual_seed(sum(shape))
     mod = torch.nn.ConvTranspose3d(128, 1, 4, 2, 1).cuda()
     st = _ConvT1Stage(mod, in_act=in_act, dtype=torch.bfloat16)
@@ -599,7 +593,7 @@ def test_last_layer_backward_on_the_first_layer_kernels(shape, in_act):
     res = []
     for fused in (True, False):
         with debug.override(no_convt1_fused_bwd=not fused):
-            gc = _GradCtx(None)
+            gc = GradCtx()
             dx = st.bwd(G, (x,), gc)
             torch.cuda.synchronize()
             res.append((dx.float().clone(), gc.grads[mod.weight].clone(), gc.grads[mod.bias].clone()))
@@ -618,7 +612,7 @@ def test_last_layer_backward_on_the_first_layer_kernels(shape, in_act):
         assert abs(float(db) - float(G.sum())) < 1e-3 * float(G.abs().sum()) ** 0.5 + 1e-2
     assert _rel_t(res[0][0], res[1][0]) < 8e-3 and _rel_t(res[0][1], res[1][1]) < 2e-3
     # the wgrad-only form used by the adaptive adversarial weight
-    gc = _GradCtx(None)
+    gc = GradCtx()
     assert st.bwd(G, (x,), gc, wgrad_only=True) is None
     assert _rel_t(gc.grads[mod.weight], res[0][1]) < 1e-5
 

@@ -7,6 +7,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import conv_bounds as cb
+from grad_stand_in import Grads
 
 pytestmark = pytest.mark.gpu
 
@@ -137,17 +138,6 @@ def test_convop_geometry_within_fp64_bound(row, dt, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- one-channel stages
-class _Grads:
-    def __init__(self, params):
-        self.b = {id(p): torch.zeros(p.shape, device=DEV) for p in params}
-
-    def buf(self, p):
-        return self.b[id(p)]
-
-    def done(self, *ps):
-        pass
-
-
 def _both16(t):
     t = torch.where(t.abs() < 2.0 ** -10, torch.zeros_like(t), t)
     return cb.rounded(t, "bf16")
@@ -181,7 +171,7 @@ def test_conv1_stage_taps_route(tup, cout, dt):
     x64, w64 = x.double()[:, None], w.double()
     z = fwd_ref("conv", x64, w64, b.double(), tup)
     G = _operand((N, *z.shape[2:], cout), dt, gen)
-    gr = _Grads([mod.weight, mod.bias])
+    gr = Grads([mod.weight, mod.bias])
     tape = []
     with _ffi.kernel_log() as names:
         y = st.fwd(x.to(DEV), tape)
@@ -221,13 +211,13 @@ def test_convt1_stage_taps_route(tup, C, dt):
     x64, w64 = _ncdhw(x), w.double()
     z = fwd_ref("convT", x64, w64, b.double(), tup)
     G = _operand((N, *z.shape[2:], 1), dt, gen)
-    gr = _Grads([mod.weight, mod.bias])
+    gr = Grads([mod.weight, mod.bias])
     tape = []
     with _ffi.kernel_log() as names:
         y = st.fwd(x.to(DEV).to(cb.DT[dt]), tape)
         dx = st.bwd(G.to(DEV), tape[0], gr)
         torch.cuda.synchronize()
-        gr2 = _Grads([mod.weight, mod.bias])
+        gr2 = Grads([mod.weight, mod.bias])
         assert st.bwd(G.to(DEV), tape[0], gr2, wgrad_only=True) is None                 # (BaselineVQVAE.last_layer_grad)
         torch.cuda.synchronize()
     print(sorted(names))

@@ -42,7 +42,7 @@ def test_adversarial_iteration_matches_oracle(adaptive, crit, epoch):
     flat, d_flat = FlatParams(net.parameters()), FlatParams(disc.parameters())
     opt, d_opt = FusedAdam(flat, lr=1e-3), FusedAdam(d_flat, lr=5e-4)
     opt.on_step.append(net.invalidate_packed_weights)
-    d_opt.on_step.append(lambda: [s.op.invalidate() for s in disc._stages])
+    d_opt.on_step.append(disc.invalidate_packed_weights)
     captured = {}
     for name, o, f in (("g", opt, flat), ("d", d_opt, d_flat)):
         def hooked(grad_scale=1.0, _o=o, _f=f, _n=name, _step=o.step):

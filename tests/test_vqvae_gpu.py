@@ -247,7 +247,8 @@ def test_fused_residual_block_matches_two_launch_path(shape):
 def test_residual_layer_with_dropout_matches_torch(dtype):
     """ResidualLayer with p_dropout > 0 (baseline.py:150-160: Conv3d -> ReLU -> Dropout3d -> Conv3d 1x1x1, + x, ReLU) in TRAINING mode: forward, data gradient and
     all four parameter gradients against torch on the CPU with the SAME channel mask; eval mode ignores the dropout (the fused block)."""
-    from synthanatomy_amd.networks.vqvae.baseline import ResidualLayer, _GradCtx, _ResStage
+    from synthanatomy_amd.networks.vqvae.baseline import ResidualLayer, _ResStage
+    from synthanatomy_amd.runtime.backward import GradCtx
     torch.manual_seed(11)
     C, p = 128, 0.3
     mod = ResidualLayer(C, C, p).cuda().train()
@@ -264,7 +265,7 @@ def test_residual_layer_with_dropout_matches_torch(dtype):
     G = (torch.randn(2, 6, 7, 9, C) * 0.1).to(dtype)
     tape = []
     y = st.fwd(x.cuda(), tape)
-    gc = _GradCtx(None)
+    gc = GradCtx()
     Gm = (G.cuda().float() * (y.float() > 0)).to(dtype)      # (the ReLU mask of a stage's OUTPUT is applied by the stage behind it: hand bwd the masked gradient)
     dx = st.bwd(Gm, tape[0], gc)
     torch.cuda.synchronize()

@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from synthanatomy_amd import _ffi, engine
-from synthanatomy_amd.networks.vqvae.baseline import ResidualLayer, _GradCtx, _ResStage
+from synthanatomy_amd.networks.vqvae.baseline import ResidualLayer, _ResStage
 
 
 def timeit(fn, n):
