@@ -358,6 +358,14 @@ int sa_embed_step(int ntab, const float *const *tables, const int64_t *const *id
  * block per row; the last one to finish advances *pos). */
 int sa_sample_step(const float *logits, int B, int V, float temperature, const float *u, int u_stride, int do_sample, int top_k, int64_t *seq, int total, int P,
                    int *pos, int *ticket, int64_t *tok, void *stream);
+/* The decision of one HEALING step (Performer.heal; the reference's decision rule, transformer.py:11-56, applied to a position that already holds a token):
+ * same grid rules, uniforms, pos / ticket / tok as sa_sample_step.  With np = *pos + 1 and x = seq[b, np]: positions np < P (and np >= total) are neither
+ * scored nor replaced.  Otherwise nll[b, np] = logsumexp_v(logits[b, v]) - logits[b, x] from the RAW logits (temperature 1, no top-k cut: the number
+ * sa_cross_entropy_rows gives for the row; +inf for x outside [0, V)); when -nll[b, np] < log_threshold, seq[b, np] receives sa_sample_step's draw (the same
+ * device code, on the temperature-scaled and top-k-cut logits) and replaced[b, np] = 1, else seq stays and replaced[b, np] = 0.  log_threshold = -inf never
+ * replaces and never draws; any log_threshold > 0 always replaces, which makes the launch sa_sample_step.  nll, replaced: [B, total].  P >= 1. */
+int sa_heal_step(const float *logits, int B, int V, float temperature, const float *u, int u_stride, int do_sample, int top_k, float log_threshold,
+                 int64_t *seq, int total, int P, float *nll, unsigned char *replaced, int *pos, int *ticket, int64_t *tok, void *stream);
 int sa_favor_step(const float *q, int q_stride, int q_off, const float *k, int k_stride, int k_off, const float *v, int v_stride, int v_off,
                   const float *proj, int B, int G, int dh, int m, int LDF, float *smax, int *kmax, float *dd, float *E, float *Ez, float *V1,
                   const int *pos, float *out, int out_stride, int out_off, void *stream);

@@ -2,11 +2,14 @@
 """Transformer entry point with the reference's flags and modes (reference run_transformer.py:405-635):
 
     python run_transformer.py run --training_subjects=<dir of *_quantization_0.npy | synthetic:64> --validation_subjects=... \\
-        --project_directory=/tmp/proj/ --experiment_name=exp --mode=training|inference --vocab_size=2048 --n_embd=512 ...
+        --project_directory=/tmp/proj/ --experiment_name=exp --mode=training|inference|healing --vocab_size=2048 --n_embd=512 ...
 
 Training: codes -> ordering -> BOS pad -> Performer -> cross entropy, Adam, per-iteration ExponentialLR.  Inference: sample
 ``prod(spatial_shape)`` tokens autoregressively, revert the ordering and write uint16 ``.npy`` code grids (postfix "sample")
-that ``run_vqvae.py --mode=decoding`` consumes.  ``--n_embed`` is accepted as an alias of ``--n_embd`` (README vs. code).
+that ``run_vqvae.py --mode=decoding`` consumes.  Healing (anomaly detection): score every token of the validation subjects' code grids
+with p(x_t | x_<t), resample those below ``--resample_threshold`` from the model in sequence order and write ``_healed_sample`` (uint16, decodable like a
+sample), ``_nll`` (float32, nats) and ``_resampled`` (uint8) grids per subject; without a threshold the codes are only scored.
+``--n_embed`` is accepted as an alias of ``--n_embd`` (README vs. code).
 
 Conditioning (reference run_transformer.py:81-95,160-215,340-373): ``--conditioning_path=<csv|tsv with a 'subject' column> --conditionings=(age,sex)
 --conditioning_type=bos_replacement|prepending`` trains on / samples for the subjects the file covers, each conditioned on its own row.
@@ -32,6 +35,8 @@ DEFAULTS = dict(
     attn_dropout=0.0, use_rezero=False, position_emb="absolute", spatial_position_emb=None, evaluation_checkpoint="recent",
     # MI355X-only: latent grid for synthetic inputs, GEMM dtype
     spatial_shape=(10, 14, 10), compute_dtype="fp32", training_epoch_length=None,
+    # --mode=healing: tokens whose probability under the model lies below it are resampled; None scores only
+    resample_threshold=None,
 )
 
 
@@ -199,11 +204,67 @@ def inference(cfg, rank, local, world, dev):
     log(rank, f"inference done: {len(mine)} samples -> {cfg['outputs_directory']}")
 
 
+def resample_threshold(value):
+    """--resample_threshold as ``heal``'s threshold: None (score only) or a probability in (0, 1]"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < float(value) <= 1.0:
+        raise ValueError(f"--resample_threshold must be None or a probability in (0, 1], but got {value!r}")
+    return float(value)
+
+
+def checked_codes(path, cfg, gen):
+    """the code grid of one subject for healing; a code outside [0, vocab_size) has no likelihood under the model"""
+    q = _load_codes(path, cfg, gen)
+    if int(q.min()) < 0 or int(q.max()) >= cfg["vocab_size"]:
+        raise ValueError(f"{path}: codes in [{int(q.min())}, {int(q.max())}] but --vocab_size={cfg['vocab_size']} allows [0, {cfg['vocab_size']})")
+    return q
+
+
+def save_healing(healed, nll, replaced, outputs_directory, filename):
+    """the three grids of one healed subject, next to where inference writes its sample: ``_healed_sample`` ends in ``_sample.npy``, so the decoding stage
+    lists it and neither of the other two"""
+    return (save_npy(healed, outputs_directory, filename, "healed_sample", np.uint16), save_npy(nll, outputs_directory, filename, "nll", np.float32),
+            save_npy(replaced, outputs_directory, filename, "resampled", np.uint8))
+
+
+def healing(cfg, rank, local, world, dev):
+    from synthanatomy_amd.utils.transformer import conditioning_batch, prepare_inference_batch
+    threshold = resample_threshold(cfg["resample_threshold"])
+    files, cond_values = _conditioned_subjects(list_inputs(cfg["validation_subjects"], postfix="quantization_0"), cfg, rank, "validation")
+    mine = list(range(len(files)))[rank::world]
+    gen = torch.Generator().manual_seed(cfg["seed"] + rank)
+    dims = tuple(_load_codes(files[0], cfg, gen).shape)
+    net, ordering = build(cfg, dims, dev)
+    path = check_for_checkpoints(cfg)
+    if path:
+        load_network_state(net, path)
+    net.eval()
+    how = dict(stateful=True) if cfg["conditionings"] and cfg["conditioning_type"] == "prepending" else {}
+    for i in range(0, len(mine), cfg["eval_batch_size"]):
+        picks = mine[i:i + cfg["eval_batch_size"]]
+        q = torch.stack([checked_codes(files[k], cfg, gen) for k in picks])
+        batch = {"quantization": q, **conditioning_batch(cond_values, cfg["conditionings"], picks)}
+        (_, cond), _ = prepare_inference_batch(batch, cfg["vocab_size"], cfg["conditionings"], device=dev)
+        healed, nll, replaced = net.heal(q, conditioning=cond, threshold=threshold, temperature=cfg["temperature"], sample=cfg["sample"], top_k=cfg["top_k"],
+                                         **how)
+        for j, k in enumerate(picks):
+            save_healing(healed[j].cpu().numpy(), nll[j].cpu().numpy(), replaced[j].cpu().numpy(), cfg["outputs_directory"], files[k])
+            print(f"[rank {rank}] {os.path.basename(files[k])}: mean nll {float(nll[j].mean()):.5f} nats, {int(replaced[j].sum())} of {replaced[j].numel()} "
+                  f"tokens resampled", flush=True)
+    log(rank, f"healing done: {len(mine)} subjects -> {cfg['outputs_directory']}")
+
+
+MODES = dict(training=training, inference=inference, healing=healing)
+
+
 def run(argv):
     from synthanatomy_amd.runtime.ddp import init_distributed
     cfg = parse_flags(argv, DEFAULTS, aliases={"n_embed": "n_embd"})
-    if cfg["mode"] not in ("training", "inference"):
-        raise ValueError(f"Transformer mode unknown. Was given {cfg['mode']} but choices are ['training', 'inference'].")
+    if cfg["mode"] not in MODES:
+        raise ValueError(f"Transformer mode unknown. Was given {cfg['mode']} but choices are {list(MODES)}.")
+    if cfg["mode"] == "healing":
+        resample_threshold(cfg["resample_threshold"])     # refuses before anything touches the device
     from synthanatomy_amd.utils.transformer import conditioning_flags
     cfg["conditionings"] = conditioning_flags(cfg["conditioning_path"], cfg["conditionings"], cfg["conditioning_type"])   # they act or refuse: never ignored
     rank, local, world = init_distributed()
@@ -219,7 +280,7 @@ def run(argv):
         log(rank, "--deterministic: fixed-order reductions (csrc/deterministic.hip); slower than the default path")
     create_folder_structure(cfg)
     dev = torch.device("cuda", local)
-    (training if cfg["mode"] == "training" else inference)(cfg, rank, local, world, dev)
+    MODES[cfg["mode"]](cfg, rank, local, world, dev)
 
 
 if __name__ == "__main__":

@@ -1258,158 +1258,151 @@ __global__ void embed_step_kernel(const EmbedArgs a, const int* __restrict__ pos
 __device__ __forceinline__ unsigned f2ukey(float f) { const unsigned i = __float_as_uint(f); return (i & 0x80000000u) ? ~i : (i | 0x80000000u); }   // unsigned order = float order
 __device__ __forceinline__ float ukey2f(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-__global__ __launch_bounds__(1024) void sample_step_kernel(const float* __restrict__ logits, int B, int V, float inv_temp, const float* __restrict__ u, int u_stride,
-                                                         int do_sample, int top_k, int64_t* __restrict__ seq, int total, int P, int* __restrict__ pos,
-                                                         int* __restrict__ ticket, int64_t* __restrict__ tok) {
-    __shared__ float sred[16];
-    __shared__ int sidx[16];
-    __shared__ float sscan[16];
-    __shared__ int sfound, slast;
-    __shared__ int shist[256];
-    __shared__ int swtot[4];
-    __shared__ unsigned sprefix;
-    __shared__ int skrem;
+// LDS of one decision block (sample_step_kernel and heal_step_kernel share the row maximum and the draw below, so the two cannot drift apart)
+struct DecideSmem {
+    float sred[16];
+    int sidx[16];
+    float sscan[16];
+    int sfound, slast;
+    int shist[256];
+    int swtot[4];
+    unsigned sprefix;
+    int skrem;
+};
+
+// maximum of the scaled row and its lowest index, in every thread (ends behind a barrier; am stays 0x7fffffff when no element ever compared greater)
+__device__ __forceinline__ void decide_row_max(const float* __restrict__ lr, int V, int ept, float inv_temp, DecideSmem& sm, float& mx, int& am) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int p = *pos;
-    const int ept = (V + 1023) / 1024;                 // elements per thread, contiguous: thread t owns [t * ept, (t + 1) * ept)
-    const bool per_row = gridDim.x > 1;
-    const float* const ur = u ? u + (int64_t)p * u_stride : nullptr;
-    for (int b = per_row ? (int)blockIdx.x : 0; b < (per_row ? (int)blockIdx.x + 1 : B); ++b) {
-        const float* lr = logits + (int64_t)b * V;
-        // row maximum (and its lowest index)
-        float mx = -INFINITY;
-        int am = 0x7fffffff;
+    mx = -INFINITY;
+    am = 0x7fffffff;
+    for (int e = 0; e < ept; ++e) {
+        const int v = tid * ept + e;
+        if (v < V) {
+            const float x = lr[v] * inv_temp;
+            if (x > mx) { mx = x; am = v; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(mx, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        const bool t0 = (om > mx) | ((om == mx) & (oa < am));
+        mx = t0 ? om : mx;
+        am = t0 ? oa : am;
+    }
+    if (lane == 0) { sm.sred[wv] = mx; sm.sidx[wv] = am; }
+    __syncthreads();
+    mx = sm.sred[0];
+    am = sm.sidx[0];
+    for (int w = 1; w < 16; ++w) {
+        const bool t0 = (sm.sred[w] > mx) | ((sm.sred[w] == mx) & (sm.sidx[w] < am));
+        mx = t0 ? sm.sred[w] : mx;
+        am = t0 ? sm.sidx[w] : am;
+    }
+}
+
+// the categorical draw of one row against the uniform ub, given decide_row_max's mx; called by every thread of the block (it holds barriers)
+__device__ __forceinline__ int decide_row_draw(const float* __restrict__ lr, int V, int ept, float inv_temp, int top_k, float mx, float ub, DecideSmem& sm) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // top-k cut: the k-th largest scaled logit by a four-pass radix select over order-preserving keys (256-bin histogram of the keys that share the
+    // digits chosen so far; the digit whose suffix count reaches the remaining k is the next one)
+    float kth = -INFINITY;
+    if (top_k > 0 && top_k < V) {
+        if (tid == 0) { sm.sprefix = 0u; sm.skrem = top_k; }
+        for (int pass = 0; pass < 4; ++pass) {
+            const int shift = 24 - 8 * pass;
+            if (tid < 256) sm.shist[tid] = 0;
+            __syncthreads();
+            const unsigned pref = sm.sprefix, pmask = pass ? (0xffffffffu << (shift + 8)) : 0u;
+            const int krem = sm.skrem;
+            for (int e = 0; e < ept; ++e) {
+                const int v = tid * ept + e;
+                if (v < V) {
+                    const unsigned key = f2ukey(lr[v] * inv_temp);
+                    if ((key & pmask) == pref) atomicAdd(&sm.shist[(key >> shift) & 0xffu], 1);
+                }
+            }
+            __syncthreads();
+            int c = 0, inc = 0;
+            if (tid < 256) {
+                c = sm.shist[tid];
+                inc = c;               // inclusive suffix count inside the wave: keys of this pass with digit >= tid
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int t = __shfl_down(inc, o, 64);
+                    if (lane + o < 64) inc += t;
+                }
+                if (lane == 0) sm.swtot[wv] = inc;
+            }
+            __syncthreads();
+            if (tid < 256) {
+                for (int w = wv + 1; w < 4; ++w) inc += sm.swtot[w];
+                if (inc >= krem && inc - c < krem) {        // exactly one digit: the suffix counts are monotone
+                    sm.sprefix = pref | ((unsigned)tid << shift);
+                    sm.skrem = krem - (inc - c);
+                }
+            }
+            __syncthreads();
+        }
+        kth = ukey2f(sm.sprefix);
+    }
+    // prefix of exp(x - max) over the kept elements in index order: per-thread sums -> wave scan -> scan of the 16 wave totals
+    float loc = 0.f;
+    for (int e = 0; e < ept; ++e) {
+        const int v = tid * ept + e;
+        if (v < V) {
+            const float x = lr[v] * inv_temp;
+            loc += x < kth ? 0.f : __expf(x - mx);
+        }
+    }
+    float inc = loc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();               // (sred / sidx of the maximum have been read by everyone)
+    if (lane == 63) sm.sscan[wv] = inc;
+    if (tid == 0) { sm.sfound = 0x7fffffff; sm.slast = -1; }
+    __syncthreads();
+    float wbase = 0.f, tot = 0.f;
+    for (int w = 0; w < 16; ++w) {
+        if (w < wv) wbase += sm.sscan[w];
+        tot += sm.sscan[w];
+    }
+    const float target = ub * tot;
+    float run = wbase + inc - loc;  // cdf before this thread's first element
+    // the first token of non-zero probability whose inclusive cdf reaches the target: every thread that owns probability mass walks its elements and
+    // offers its first hit; the lowest index wins.  No "is the target inside my interval" test -- neighbouring threads' differently associated sums
+    // can leave one-ulp gaps between intervals -- and a token the top-k cut removed (or with exp() = 0) can never be returned.
+    int hit = 0x7fffffff, lastnz = -1;
+    if (loc > 0.f) {
         for (int e = 0; e < ept; ++e) {
             const int v = tid * ept + e;
             if (v < V) {
                 const float x = lr[v] * inv_temp;
-                if (x > mx) { mx = x; am = v; }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float om = __shfl_xor(mx, o, 64);
-            const int oa = __shfl_xor(am, o, 64);
-            const bool t0 = (om > mx) | ((om == mx) & (oa < am));
-            mx = t0 ? om : mx;
-            am = t0 ? oa : am;
-        }
-        if (lane == 0) { sred[wv] = mx; sidx[wv] = am; }
-        __syncthreads();
-        mx = sred[0];
-        am = sidx[0];
-        for (int w = 1; w < 16; ++w) {
-            const bool t0 = (sred[w] > mx) | ((sred[w] == mx) & (sidx[w] < am));
-            mx = t0 ? sred[w] : mx;
-            am = t0 ? sidx[w] : am;
-        }
-        int ix = min(am, V - 1);                       // (all-NaN row: no element ever compared greater)
-        if (do_sample) {
-            // top-k cut: the k-th largest scaled logit by a four-pass radix select over order-preserving keys (256-bin histogram of the keys that share the
-            // digits chosen so far; the digit whose suffix count reaches the remaining k is the next one)
-            float kth = -INFINITY;
-            if (top_k > 0 && top_k < V) {
-                if (tid == 0) { sprefix = 0u; skrem = top_k; }
-                for (int pass = 0; pass < 4; ++pass) {
-                    const int shift = 24 - 8 * pass;
-                    if (tid < 256) shist[tid] = 0;
-                    __syncthreads();
-                    const unsigned pref = sprefix, pmask = pass ? (0xffffffffu << (shift + 8)) : 0u;
-                    const int krem = skrem;
-                    for (int e = 0; e < ept; ++e) {
-                        const int v = tid * ept + e;
-                        if (v < V) {
-                            const unsigned key = f2ukey(lr[v] * inv_temp);
-                            if ((key & pmask) == pref) atomicAdd(&shist[(key >> shift) & 0xffu], 1);
-                        }
-                    }
-                    __syncthreads();
-                    int c = 0, inc = 0;
-                    if (tid < 256) {
-                        c = shist[tid];
-                        inc = c;               // inclusive suffix count inside the wave: keys of this pass with digit >= tid
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1) {
-                            const int t = __shfl_down(inc, o, 64);
-                            if (lane + o < 64) inc += t;
-                        }
-                        if (lane == 0) swtot[wv] = inc;
-                    }
-                    __syncthreads();
-                    if (tid < 256) {
-                        for (int w = wv + 1; w < 4; ++w) inc += swtot[w];
-                        if (inc >= krem && inc - c < krem) {        // exactly one digit: the suffix counts are monotone
-                            sprefix = pref | ((unsigned)tid << shift);
-                            skrem = krem - (inc - c);
-                        }
-                    }
-                    __syncthreads();
-                }
-                kth = ukey2f(sprefix);
-            }
-            // prefix of exp(x - max) over the kept elements in index order: per-thread sums -> wave scan -> scan of the 16 wave totals
-            float loc = 0.f;
-            for (int e = 0; e < ept; ++e) {
-                const int v = tid * ept + e;
-                if (v < V) {
-                    const float x = lr[v] * inv_temp;
-                    loc += x < kth ? 0.f : __expf(x - mx);
+                const float pe = x < kth ? 0.f : __expf(x - mx);
+                run += pe;
+                if (pe > 0.f) {
+                    lastnz = v;
+                    if (run >= target && hit == 0x7fffffff) hit = v;
                 }
             }
-            float inc = loc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float t = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += t;
-            }
-            __syncthreads();               // (sred / sidx of the maximum have been read by everyone)
-            if (lane == 63) sscan[wv] = inc;
-            if (tid == 0) { sfound = 0x7fffffff; slast = -1; }
-            __syncthreads();
-            float wbase = 0.f, tot = 0.f;
-            for (int w = 0; w < 16; ++w) {
-                if (w < wv) wbase += sscan[w];
-                tot += sscan[w];
-            }
-            const float target = ur[b] * tot;
-            float run = wbase + inc - loc;  // cdf before this thread's first element
-            // the first token of non-zero probability whose inclusive cdf reaches the target: every thread that owns probability mass walks its elements and
-            // offers its first hit; the lowest index wins.  No "is the target inside my interval" test -- neighbouring threads' differently associated sums
-            // can leave one-ulp gaps between intervals -- and a token the top-k cut removed (or with exp() = 0) can never be returned.
-            int hit = 0x7fffffff, lastnz = -1;
-            if (loc > 0.f) {
-                for (int e = 0; e < ept; ++e) {
-                    const int v = tid * ept + e;
-                    if (v < V) {
-                        const float x = lr[v] * inv_temp;
-                        const float pe = x < kth ? 0.f : __expf(x - mx);
-                        run += pe;
-                        if (pe > 0.f) {
-                            lastnz = v;
-                            if (run >= target && hit == 0x7fffffff) hit = v;
-                        }
-                    }
-                }
-            }
-            if (hit != 0x7fffffff) atomicMin(&sfound, hit);
-            __syncthreads();
-            if (sfound == 0x7fffffff) {     // rounding left every recomputed cdf value below the target (u close to 1): the last token that carries mass
-                if (lastnz >= 0) atomicMax(&slast, lastnz);
-                __syncthreads();
-                ix = max(slast, 0);
-            } else
-                ix = sfound;
         }
-        if (tid == 0) {
-            const int np = p + 1;
-            if (np < total) {
-                if (np >= P) seq[(int64_t)b * total + np] = ix;
-                tok[b] = seq[(int64_t)b * total + np];
-            }
-        }
-        __syncthreads();
     }
-    if (tid == 0) {
+    if (hit != 0x7fffffff) atomicMin(&sm.sfound, hit);
+    __syncthreads();
+    if (sm.sfound == 0x7fffffff) {     // rounding left every recomputed cdf value below the target (u close to 1): the last token that carries mass
+        if (lastnz >= 0) atomicMax(&sm.slast, lastnz);
+        __syncthreads();
+        return max(sm.slast, 0);
+    }
+    return sm.sfound;
+}
+
+// the end of a decision launch: *pos += 1, by the one block or by the last of the per-row blocks (which re-zeroes the ticket)
+__device__ __forceinline__ void decide_advance(bool per_row, int B, int p, int* __restrict__ pos, int* __restrict__ ticket) {
+    if (threadIdx.x == 0) {
         if (!per_row) *pos = p + 1;
         else {
             __threadfence();
@@ -1419,6 +1412,88 @@ __global__ __launch_bounds__(1024) void sample_step_kernel(const float* __restri
             }
         }
     }
+}
+
+__global__ __launch_bounds__(1024) void sample_step_kernel(const float* __restrict__ logits, int B, int V, float inv_temp, const float* __restrict__ u, int u_stride,
+                                                         int do_sample, int top_k, int64_t* __restrict__ seq, int total, int P, int* __restrict__ pos,
+                                                         int* __restrict__ ticket, int64_t* __restrict__ tok) {
+    __shared__ DecideSmem sm;
+    const int tid = threadIdx.x;
+    const int p = *pos;
+    const int ept = (V + 1023) / 1024;                 // elements per thread, contiguous: thread t owns [t * ept, (t + 1) * ept)
+    const bool per_row = gridDim.x > 1;
+    const float* const ur = u ? u + (int64_t)p * u_stride : nullptr;
+    for (int b = per_row ? (int)blockIdx.x : 0; b < (per_row ? (int)blockIdx.x + 1 : B); ++b) {
+        const float* lr = logits + (int64_t)b * V;
+        float mx;
+        int am;
+        decide_row_max(lr, V, ept, inv_temp, sm, mx, am);
+        int ix = min(am, V - 1);                       // (all-NaN row: no element ever compared greater)
+        if (do_sample) ix = decide_row_draw(lr, V, ept, inv_temp, top_k, mx, ur[b], sm);
+        if (tid == 0) {
+            const int np = p + 1;
+            if (np < total) {
+                if (np >= P) seq[(int64_t)b * total + np] = ix;
+                tok[b] = seq[(int64_t)b * total + np];
+            }
+        }
+        __syncthreads();
+    }
+    decide_advance(per_row, B, p, pos, ticket);
+}
+
+// ---- healing step (Performer.heal): sample_step_kernel's grid rules and uniforms, but position pos + 1 already HOLDS a token x.  It is scored with the
+// model's own likelihood -- nll = logsumexp(raw logits) - logits[x]: temperature 1, no top-k cut, what ce_rows_kernel gives for the row -- and replaced by
+// sample_step_kernel's draw (decide_row_draw / the arg-max, on the scaled and cut logits) only when -nll < log_threshold.  The scaled maximum sits at the
+// raw row's maximum (T > 0; on a tie among the scaled values the lowest index is within one rounding of it, which a max shift does not mind), so the raw
+// log-sum-exp costs one more pass: per-thread sums of its contiguous elements -> wave_sum -> the 16 wave totals in order.  log_threshold = -inf never
+// replaces and never draws; any log_threshold > 0 always replaces (an all-NaN row too: that limit IS the sampler).  Prefix entries (< P) and np >= total
+// are neither scored nor replaced.
+__global__ __launch_bounds__(1024) void heal_step_kernel(const float* __restrict__ logits, int B, int V, float inv_temp, const float* __restrict__ u, int u_stride,
+                                                       int do_sample, int top_k, float log_threshold, int64_t* __restrict__ seq, int total, int P,
+                                                       float* __restrict__ nll, unsigned char* __restrict__ replaced, int* __restrict__ pos,
+                                                       int* __restrict__ ticket, int64_t* __restrict__ tok) {
+    __shared__ DecideSmem sm;
+    __shared__ float ssum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int p = *pos, np = p + 1;
+    const int ept = (V + 1023) / 1024;
+    const bool per_row = gridDim.x > 1;
+    const float* const ur = u ? u + (int64_t)p * u_stride : nullptr;
+    for (int b = per_row ? (int)blockIdx.x : 0; b < (per_row ? (int)blockIdx.x + 1 : B); ++b) {
+        if (np >= total || np < P) {                   // (uniform over the block)
+            if (tid == 0 && np < total) tok[b] = seq[(int64_t)b * total + np];
+            continue;
+        }
+        const float* lr = logits + (int64_t)b * V;
+        float mx;
+        int am;
+        decide_row_max(lr, V, ept, inv_temp, sm, mx, am);
+        int ix = min(am, V - 1);
+        const float m = lr[ix];
+        float loc = 0.f;
+        for (int e = 0; e < ept; ++e) {
+            const int v = tid * ept + e;
+            if (v < V) loc += expf(lr[v] - m);
+        }
+        loc = wave_sum(loc);
+        if (lane == 0) ssum[wv] = loc;
+        __syncthreads();
+        float s = ssum[0];
+        for (int w = 1; w < 16; ++w) s += ssum[w];
+        const int64_t x = seq[(int64_t)b * total + np];
+        const float score = (x >= 0 && x < (int64_t)V) ? (m + logf(s)) - lr[x] : INFINITY;
+        const bool repl = log_threshold > 0.f || -score < log_threshold;     // every thread holds the same s: uniform over the block
+        if (repl && do_sample) ix = decide_row_draw(lr, V, ept, inv_temp, top_k, mx, ur[b], sm);
+        if (tid == 0) {
+            nll[(int64_t)b * total + np] = score;
+            replaced[(int64_t)b * total + np] = repl ? 1 : 0;
+            tok[b] = repl ? (int64_t)ix : x;
+            if (repl) seq[(int64_t)b * total + np] = ix;
+        }
+        __syncthreads();
+    }
+    decide_advance(per_row, B, p, pos, ticket);
 }
 
 // Phase A of a global-head step, one block per (batch, head): projections dd[m] = x . P[m] (P carries the data normaliser) of the new
@@ -2273,6 +2348,17 @@ extern "C" int sa_sample_step(const float* logits, int B, int V, float temperatu
     if (!logits || !seq || !pos || !tok || (do_sample && !u) || u_stride < 0 || B <= 0 || V <= 0 || total <= 0 || !(temperature > 0.f)) return SA_EINVAL;
     SA_LAUNCH(sample_step_kernel, dim3(ticket ? B : 1), dim3(1024), 0, ST(stream), logits, B, V, 1.f / temperature, u, u_stride, do_sample, top_k, seq, total, P, pos,
               ticket, tok);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sa_heal_step(const float* logits, int B, int V, float temperature, const float* u, int u_stride, int do_sample, int top_k, float log_threshold,
+                            int64_t* seq, int total, int P, float* nll, unsigned char* replaced, int* pos, int* ticket, int64_t* tok, void* stream) {
+    if (!logits || !seq || !nll || !replaced || !pos || !tok || (do_sample && !u) || u_stride < 0 || B <= 0 || V <= 0 || total <= 0 || P < 1 ||
+        !(temperature > 0.f) || log_threshold != log_threshold)
+        return SA_EINVAL;
+    SA_LAUNCH(heal_step_kernel, dim3(ticket ? B : 1), dim3(1024), 0, ST(stream), logits, B, V, 1.f / temperature, u, u_stride, do_sample, top_k, log_threshold, seq,
+              total, P, nll, replaced, pos, ticket, tok);
     SA_CHECK_LAUNCH();
     return 0;
 }

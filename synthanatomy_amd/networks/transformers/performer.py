@@ -28,7 +28,7 @@ from ... import engine as _engine
 from ...engine import ConvOp, Repack, _ru
 from ...runtime.backward import GradCtx, side_wgrad
 from .img2seq_ordering import Ordering
-from .transformer import TransformerBase, sequence_to_grid
+from .transformer import TransformerBase, heal_log_threshold, sequence_to_grid
 
 
 class TransformerConditioningType(Enum):  # src/utils/transformer.py:21-24
@@ -1329,7 +1329,34 @@ class Performer(TransformerBase):
             "stateful sampling takes conditionings only with conditioning_type 'bos_replacement' or 'prepending' (use stateful=False)")
         return self._sample_stateful(prefix, temperature, sample, top_k, use_graph, conditioning)
 
+    @torch.no_grad()
+    def heal(self, codes: torch.Tensor, conditioning: torch.Tensor = None, threshold: Optional[float] = None, temperature: float = 1.0, sample: bool = True,
+             top_k: Optional[int] = None, stateful: Optional[bool] = None, use_graph: bool = True):
+        """TransformerBase.heal on the O(N) decoder: the driver of ``sample`` with the whole ordered sequence behind the BOS / conditioning entries and
+        ``sa_heal_step`` instead of ``sa_sample_step`` closing each step (the same launches per token).  ``stateful`` selects the path as in ``sample``;
+        ``stateful=False`` is the reference-faithful loop of the base class."""
+        bos = self.conditioning_type == TransformerConditioningType.BOSREPLACEMENT.value
+        if stateful is None:
+            stateful = (conditioning is None or bos) and self.layer_pos_emb is None
+        if stateful and self.layer_pos_emb is not None:
+            raise NotImplementedError("stateful (O(N)) healing does not rotate the global heads' q / k (rotary_position_emb=True): use stateful=False")
+        if not stateful:
+            return super().heal(codes, conditioning=conditioning, threshold=threshold, temperature=temperature, sample=sample, top_k=top_k)
+        assert not conditioning or self.conditioning_type != TransformerConditioningType.NONE.value, (
+            "stateful healing takes conditionings only with conditioning_type 'bos_replacement' or 'prepending' (use stateful=False)")
+        log_threshold = heal_log_threshold(threshold)
+        dev = self.token_emb.weight.device
+        body = codes.reshape(codes.shape[0], -1)[:, self.ordering.get_sequence_ordering()].long().to(dev)
+        prefix = torch.full((body.shape[0], 1), self.bos_token(), dtype=torch.int64, device=dev)
+        return self._decode_stateful(prefix, temperature, sample, top_k, use_graph, conditioning, body=body, log_threshold=log_threshold)
+
     def _sample_stateful(self, prefix, temperature, sample, top_k, use_graph, conditioning=None):
+        return self._decode_stateful(prefix, temperature, sample, top_k, use_graph, conditioning)
+
+    def _decode_stateful(self, prefix, temperature, sample, top_k, use_graph, conditioning=None, body=None, log_threshold=None):
+        """The O(N) driver of ``sample`` (``body`` None) and ``heal`` (``body`` [B, steps]: the ordered sequence to score, ``log_threshold`` the decision's
+        log-probability): embedding tables, conditioning rows, per-layer states, warm-up step, capture and replay loop are one code; the two differ in how
+        ``seq`` starts, in the decision kernel that closes the step and in the two buffers that kernel fills."""
         _ffi.require_gpu()
         self.eval()
         dev = self.token_emb.weight.device
@@ -1346,6 +1373,12 @@ class Performer(TransformerBase):
         assert npos <= self.max_seq_len, f"sequence length {npos} must be less than the max sequence length {self.max_seq_len}"
         seq = torch.zeros(B, total, dtype=torch.int64, device=dev)
         seq[:, c:P] = prefix.to(dev).long()
+        healing = body is not None
+        if healing:
+            assert tuple(body.shape) == (B, steps), f"codes of {tuple(body.shape)} entries, but the ordering covers {(B, steps)}"
+            seq[:, P:] = body
+            nll = torch.zeros(B, total, dtype=torch.float32, device=dev)
+            replaced = torch.zeros(B, total, dtype=torch.uint8, device=dev)
         posbuf = torch.zeros(2, dtype=torch.int32, device=dev)     # [position, ticket word of sa_sample_step]
         pos, ticket = posbuf[:1], posbuf[1:]
         tok = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -1381,7 +1414,8 @@ class Performer(TransformerBase):
         col = torch.arange(total, device=dev)[None, :]
         tok.copy_(seq0[:, 0])
 
-        fused_tail = not debug.host("no_sample_step")     # one launch for the decision (incl. the top-k cut) + sequence update (sa_sample_step)
+        # healing has no torch form of its decision: always the kernel
+        fused_tail = healing or not debug.host("no_sample_step")     # one launch for the decision (incl. the top-k cut) + sequence update (sa_sample_step)
         n_vocab = self._out_mod().weight.shape[0]
         if top_k is not None and not 0 < int(top_k) <= n_vocab:   # what torch.topk of the reference (transformer.py:14) raises on
             raise RuntimeError(f"selected index k out of range (top_k = {top_k}, vocabulary {n_vocab})")
@@ -1399,6 +1433,11 @@ class Performer(TransformerBase):
             h = _LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps)
             logits = torch.empty(B, n_vocab, dtype=torch.float32, device=dev)
             layers[0]._gemv(h, [self._out_mod()], logits)
+            if healing:     # sa_sample_step's launch with the score and the threshold in front of the draw
+                _ffi.check(lib.sa_heal_step(_ffi.ptr(logits), B, logits.shape[1], float(temperature), _ffi.ptr(u_all), B, int(bool(sample)), int(top_k or 0),
+                                            float(log_threshold), _ffi.ptr(seq), total, P, _ffi.ptr(nll), _ffi.ptr(replaced), _ffi.ptr(pos), _ffi.ptr(ticket),
+                                            _ffi.ptr(tok), _ffi.stream()), "sa_heal_step")
+                return
             if fused_tail:
                 # temperature, softmax, the draw (inverse CDF against the pre-drawn uniforms -- torch.multinomial cannot be captured in a HIP graph) or arg-max,
                 # seq[:, pos + 1] (unless it belongs to the given prefix), the next step's token, pos += 1: one launch instead of ~20 small torch kernels
@@ -1424,6 +1463,16 @@ class Performer(TransformerBase):
             seq.copy_(torch.where(write, ix.expand(B, total), seq))
             pos.add_(1)
 
+        def rewind():     # everything the warm-up step wrote
+            for l, stt in zip(layers, states):
+                l.reset_state(stt)
+            posbuf.zero_()
+            seq.copy_(seq0)
+            tok.copy_(seq0[:, 0])
+            if healing:
+                nll.zero_()
+                replaced.zero_()
+
         graph = None
         if use_graph:
             try:
@@ -1433,11 +1482,7 @@ class Performer(TransformerBase):
                     one_step()
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
-                for l, stt in zip(layers, states):
-                    l.reset_state(stt)
-                posbuf.zero_()
-                seq.copy_(seq0)
-                tok.copy_(seq0[:, 0])
+                rewind()
                 graph = torch.cuda.CUDAGraph()
                 # thread_local: other threads of the process (the RCCL watchdog of a distributed run) may call HIP during the capture
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -1447,16 +1492,14 @@ class Performer(TransformerBase):
                 warnings.warn(f"HIP graph capture of the decode step failed ({type(exc).__name__}: {exc}); running it eagerly")
                 graph = None
                 torch.cuda.synchronize()
-                for l, stt in zip(layers, states):
-                    l.reset_state(stt)
-                posbuf.zero_()
-                seq.copy_(seq0)
-                tok.copy_(seq0[:, 0])
+                rewind()
         for _ in range(npos):
             if graph is not None:
                 graph.replay()
             else:
                 one_step()
+        if healing:
+            return tuple(sequence_to_grid(a[:, c:], P - c, self.ordering) for a in (seq, nll, replaced.bool()))
         return sequence_to_grid(seq[:, c:], P - c, self.ordering)
 
     # ------------------------------------------------------------------------------------------------

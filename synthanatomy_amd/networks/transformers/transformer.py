@@ -10,6 +10,7 @@ Two pieces are shared by every decoding path of this build -- the reference-fait
 """
 from __future__ import annotations
 
+import math
 from typing import Any, Optional
 
 import numpy as np
@@ -36,8 +37,50 @@ def sequence_to_grid(tokens: torch.Tensor, prefix_len: int, ordering) -> torch.T
     return torch.squeeze(body.reshape(body.shape[0], *ordering.dimensions), 1)
 
 
+def heal_log_threshold(threshold: Optional[float]) -> float:
+    """the probability threshold of ``heal`` as the log-probability the decision compares with: ``None`` (score only) is -inf, which nothing lies below"""
+    if threshold is None:
+        return float("-inf")
+    if not float(threshold) > 0.0:
+        raise ValueError(f"threshold must be None or a probability > 0, but got {threshold}")
+    return math.log(float(threshold))
+
+
 class TransformerBase(torch.nn.Module):
     """Abstract class for transformers."""
+
+    @torch.no_grad()
+    def heal(self, codes: torch.Tensor, conditioning: torch.Tensor = None, threshold: Optional[float] = None, temperature: float = 1.0, sample: bool = True,
+             top_k: Optional[int] = None):
+        """Score an existing code grid ``[B, *spatial]`` token by token with p(x_t | x_<t) and resample ("heal") the tokens whose probability lies below
+        ``threshold`` from the model, in sequence order, every later token conditioned on the already-healed prefix.  Returns ``(healed int64, nll float32
+        in nats, replaced bool)`` in the latent grid's layout.  ``threshold=None`` scores only.  The score is the log-softmax of the RAW last-row logits
+        (temperature and top-k steer the replacement draw alone, through ``choose_next``).  This is the procedure in its reference form -- one full forward
+        over the growing prefix per position, as ``sample`` -- and the comparator of the O(N) decoder of ``performer.Performer``."""
+        self.eval()
+        log_threshold = heal_log_threshold(threshold)
+        n_new = int(np.prod(self.ordering.dimensions))
+        dev = next(self.parameters()).device
+        body = codes.reshape(codes.shape[0], -1)[:, self.ordering.get_sequence_ordering()].long().to(dev)
+        assert body.shape[1] == n_new, f"codes of {body.shape[1]} entries, but the ordering covers {n_new}"
+        seq = torch.cat((torch.full_like(body[:, :1], self.bos_token()), body), 1)
+        nll = torch.zeros(seq.shape, dtype=torch.float32, device=dev)
+        replaced = torch.zeros(seq.shape, dtype=torch.bool, device=dev)
+        for t in range(1, 1 + n_new):
+            logits = self(seq[:, :t], conditioning)[:, -1, :].float()
+            x = seq[:, t]
+            inside = (x >= 0) & (x < logits.shape[1])
+            logp = torch.log_softmax(logits, dim=-1).gather(1, x.clamp(0, logits.shape[1] - 1)[:, None]).squeeze(1)
+            nll[:, t] = torch.where(inside, -logp, torch.full_like(logp, float("inf")))
+            repl = (-nll[:, t] < log_threshold) | (log_threshold > 0)
+            if bool(repl.any()):
+                seq[:, t] = torch.where(repl, choose_next(logits, temperature, sample, top_k).squeeze(1), x)
+            replaced[:, t] = repl
+        return tuple(sequence_to_grid(a, 1, self.ordering) for a in (seq, nll, replaced))
+
+    def bos_token(self) -> int:
+        """the begin-of-sentence id: the entry behind the codebook in the token table (``prepare_batch`` pads the sequence with ``vocab_size``)"""
+        return self.token_emb.num_embeddings - 1
 
     @torch.no_grad()
     def sample_next_index(self, x: torch.Tensor, conditioning: torch.Tensor = None, temperature: float = 1.0, sample: bool = True,
