@@ -323,6 +323,36 @@ typedef struct sa_egress_params {
 } sa_egress_params; /* 64 bytes */
 int sa_volume_egress(const void *x, void *raw, int64_t raw_bytes, const sa_egress_params *params, void *ws, void *stream);
 int64_t sa_volume_egress_workspace_bytes(void);
+/* Voxel-space anomaly map of a healed volume (metrics/anomaly.py, run_vqvae.py --mode=anomaly; csrc/anomaly.hip; this project's own rule,
+ * no reference counterpart).  x, r [B, D, H, W] fp32 contiguous device tensors: the scan and the decoded healed codes.  m (may be NULL) [B, d, h, w] fp32:
+ * a latent weight grid, D = f_D d, H = f_H h, W = f_W w with integer factors >= 1.  label (may be NULL) [B, D, H, W] bytes: class 1 where != 0.
+ * a_out [B, D, H, W] fp32 receives the map.  params is read on the HOST.
+ *   e = |x - r| (SA_ANOMALY_ABS), max(x - r, 0) (SA_ANOMALY_POSITIVE) or max(r - x, 0) (SA_ANOMALY_NEGATIVE)
+ *   u(p) = m[p_D / f_D][p_H / f_H][p_W / f_W] inside the volume, 0 outside;   w(v) = sum over t in [-R, R]^3 of g(t_D) g(t_H) g(t_W) u(v + t) with
+ *   g(i) = taps[i + R];   a = e w, and a = e when m is NULL (taps, R, d, h, w are then ignored)
+ * results: B records of SA_ANOMALY_RESULT_WORDS 64-bit words (the call clears them first): [0] = sum a, accumulated in fp64 (the bits of a double),
+ * [1] = max a (the bits of a double holding the float), [2], [3], [4] = TP, FP, FN of [a >= threshold] against the label (0 unless has_threshold;
+ * without a label every voxel is class 0), [5..7] = 0, [8 + 256 c + k] = voxels of class c with bin k = min(255, (int)(a * inv_bin)), the product one
+ * fp32 multiply.  Three operations on the stream (a clear, the map, the per-volume sums), no host synchronisation.  The float summaries are added in a
+ * fixed order without float atomics; the map and every summary of a volume are bitwise the same alone or inside any batch, and from call to call.
+ * ws: sa_anomaly_map_workspace_bytes(params) bytes, 8-byte aligned; results 8-byte aligned.
+ * SA_EINVAL (nothing launched) for null operands, a dim < 1, with m a latent side that does not divide its side, R outside 0..SA_ANOMALY_MAX_R, an
+ * unknown residual, inv_bin not positive and finite, a non-finite threshold; SA_EUNSUPPORTED for B > 65535 and D H W >= 2^31 - 1. */
+enum { SA_ANOMALY_ABS = 0, SA_ANOMALY_POSITIVE = 1, SA_ANOMALY_NEGATIVE = 2 };
+enum { SA_ANOMALY_MAX_R = 24, SA_ANOMALY_RESULT_WORDS = 520 };
+typedef struct sa_anomaly_params {
+    int32_t B, D, H, W;
+    int32_t d, h, w;            /* the latent grid's sides (0 without m) */
+    int32_t residual;           /* SA_ANOMALY_ABS | SA_ANOMALY_POSITIVE | SA_ANOMALY_NEGATIVE */
+    int32_t R;                  /* the filter has 2 R + 1 taps */
+    int32_t has_threshold;
+    float inv_bin;              /* 256 / hist_max */
+    float threshold;
+    float taps[49];             /* 2 SA_ANOMALY_MAX_R + 1; the first 2 R + 1 are read */
+} sa_anomaly_params; /* 244 bytes */
+int sa_anomaly_map(const float *x, const float *r, const float *m, const unsigned char *label, float *a_out, const sa_anomaly_params *params,
+                   void *results, void *ws, void *stream);
+int64_t sa_anomaly_map_workspace_bytes(const sa_anomaly_params *params);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -2,7 +2,7 @@
 """VQ-VAE entry point with the reference's flags and modes (reference run_vqvae.py:538-859):
 
     python run_vqvae.py run --training_subjects=synthetic:16 --validation_subjects=synthetic:2 --project_directory=/tmp/proj/ \\
-        --experiment_name=exp --mode=training|extracting|decoding  [--no_levels=4 --no_channels=256 ...]
+        --experiment_name=exp --mode=training|extracting|decoding|anomaly  [--no_levels=4 --no_channels=256 ...]
 
 MONAI/ignite/fire/deepspeed are not on the target, so the loop is a minimal in-house one: Adam + per-iteration ExponentialLR
 (run_vqvae.py:82-91,162), losses "mse", "jukebox" (spectral), "spectral" / "hartley" / "wavegan" (FFT amplitude + phase, weighted Hartley and
@@ -32,6 +32,17 @@ file's own axes with an affine that puts the ROI where the source has it; other 
 auto-scaled to the full code range (scl_slope / scl_inter in the header).  ``--num_workers`` threads (at most 8) compress and write while the next batch
 is decoded.  The code files stay uint16 ``.npy``.  The flags act or refuse: an unknown value, an integer dtype with ``.npy``, a NIfTI extension with
 ``--mode=training`` or with ``--no_augmented_extractions > 0`` raise a ``ValueError`` before anything runs.
+
+``--mode=anomaly`` (MI355X-only; the rule is this project's own) is the last stage of the healing application: every ``--validation_subjects``
+scan goes through the usual input path, the files ``run_transformer.py --mode=healing`` wrote for its codes (``<stem>_quantization_0_healed_sample.npy``,
+``..._resampled.npy``, ``..._nll.npy``) are found by stem under ``--anomaly_codes=<dir|glob>`` (default: this experiment's outputs directory), the healed
+codes are decoded and ``sa_anomaly_map`` turns scan, decoding and the latent weight grid into ``<name>_anomaly_map`` on the device, with no file in
+between; ``<name>_healed_reconstruction`` is written next to it (``.npy``, or NIfTI with the source geometry under ``--output_ext``) and every rank
+writes ``anomaly_scores_rank<k>.csv`` (subject, sum, max and, with ``--anomaly_labels``, Dice at the threshold, the best Dice over the 256 histogram
+edges with its threshold, and the average precision).  ``--anomaly_weight=mask|nll|none`` picks the grid, ``--anomaly_sigma`` the Gaussian that smooths
+its upsampling (None: half the down-sampling factor), ``--anomaly_residual=abs|positive|negative`` the sign convention, ``--anomaly_threshold`` the
+operating point of the TP / FP / FN counts, ``--anomaly_hist_max`` the top of the histogram, ``--anomaly_labels`` any input spec of label volumes
+(matched by stem, reoriented and cropped like the scans, never normalised, class 1 where > 0.5).
 """
 import os
 import sys
@@ -57,7 +68,9 @@ DEFAULTS = dict(
     num_embeddings=(256,), embedding_dim=(256,), embedding_init=("normal",), commitment_cost=(0.25,), decay=(0.99,), decay_warmup=None,
     max_decay_epochs=50, norm=None, dropout=0.0, act="RELU", output_act=None, evaluation_checkpoint="recent", load_nii_canonical=True,
     output_ext=".npy", output_dtype="float32",
+    anomaly_codes=None, anomaly_weight="mask", anomaly_sigma=None, anomaly_residual="abs", anomaly_threshold=None, anomaly_hist_max=1.0, anomaly_labels=None,
 )
+MODES = ["training", "extracting", "decoding", "anomaly"]
 
 
 def _check_output_flags(cfg):
@@ -428,12 +441,173 @@ def inference(cfg, rank, local, world, dev):
     log(rank, f"{cfg['mode']} done: {len(files)} inputs -> {cfg['outputs_directory']}")
 
 
+def _stem(path):
+    name = os.path.basename(path)
+    for ext in (".nii.gz", ".nii", ".npy"):
+        if name.endswith(ext):
+            return name[:-len(ext)]
+    return name
+
+
+def _downsampling_factor(cfg):
+    f = 1
+    for p in list(cfg["downsample_parameters"])[:int(cfg["no_levels"])]:
+        f *= int(p[1])
+    return f
+
+
+def _anomaly_sigma(cfg):
+    """--anomaly_sigma, or half the largest down-sampling factor of the network the flags describe"""
+    return cfg["anomaly_sigma"] if cfg["anomaly_sigma"] is not None else _downsampling_factor(cfg) / 2.0
+
+
+def _check_anomaly_flags(cfg):
+    """the --anomaly_* flags act or refuse (before anything touches the device)"""
+    from synthanatomy_amd.metrics.anomaly import MAX_SIGMA, RESIDUALS
+    if cfg["anomaly_weight"] not in ("mask", "nll", "none"):
+        raise ValueError(f"--anomaly_weight={cfg['anomaly_weight']}: choices are mask, nll and none")
+    if cfg["anomaly_residual"] not in RESIDUALS:
+        raise ValueError(f"--anomaly_residual={cfg['anomaly_residual']}: choices are abs, positive and negative")
+    sigma = _anomaly_sigma(cfg)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not 0 <= sigma <= MAX_SIGMA:
+        raise ValueError(f"--anomaly_sigma={sigma}: a number in [0, {MAX_SIGMA:g}] or None (half the down-sampling factor) is needed")
+    t = cfg["anomaly_threshold"]
+    if t is not None and (isinstance(t, bool) or not isinstance(t, (int, float)) or t != t or abs(t) == float("inf")):
+        raise ValueError(f"--anomaly_threshold={t}: a finite number or None is needed")
+    hm = cfg["anomaly_hist_max"]
+    if isinstance(hm, bool) or not isinstance(hm, (int, float)) or not 0 < hm < float("inf"):
+        raise ValueError(f"--anomaly_hist_max={hm}: a finite number > 0 is needed")
+    if cfg["anomaly_codes"] is not None and not isinstance(cfg["anomaly_codes"], str):
+        raise ValueError(f"--anomaly_codes={cfg['anomaly_codes']}: a directory or a glob is needed")
+    if int(cfg["no_augmented_extractions"] or 0) > 0:
+        raise ValueError(f"--no_augmented_extractions={cfg['no_augmented_extractions']}: --mode=anomaly compares every scan with its own healed codes")
+
+
+def find_healing_outputs(subjects, spec, weight="mask"):
+    """For every subject the files ``run_transformer.save_healing`` wrote for its codes, found by stem under ``spec`` (a directory, searched recursively,
+    or a glob): ``<stem>_quantization_0_healed_sample.npy`` and next to it ``..._resampled.npy`` / ``..._nll.npy`` (``weight`` = mask / nll says which
+    one is needed).  One dict per subject (keys healed, resampled, nll); a subject with no match, or with more than one, is refused by name."""
+    import glob
+    found = set()
+    for hit in ([spec] if os.path.isdir(spec) else glob.glob(spec, recursive=True)):      # a directory the glob matches is searched like one given
+        if os.path.isdir(hit):
+            found.update(glob.glob(os.path.join(hit, "**", "*_healed_sample.npy"), recursive=True))
+        elif hit.endswith("_healed_sample.npy"):
+            found.add(hit)
+    found = sorted(found)
+    out = []
+    for s in subjects:
+        want = f"{_stem(s)}_quantization_0_healed_sample.npy"
+        hits = [f for f in found if os.path.basename(f) == want]
+        if not hits:
+            raise ValueError(f"{s}: no healing output {want} under {spec} (run_transformer.py --mode=healing writes it; see --anomaly_codes)")
+        if len(hits) > 1:
+            raise ValueError(f"{s}: {len(hits)} healing outputs named {want} under {spec} ({', '.join(hits)}): narrow --anomaly_codes")
+        base = hits[0][:-len("healed_sample.npy")]
+        rec = {"healed": hits[0], "resampled": base + "resampled.npy", "nll": base + "nll.npy"}
+        need = {"mask": "resampled", "nll": "nll"}.get(weight)
+        if need and not os.path.exists(rec[need]):
+            raise ValueError(f"{s}: {os.path.basename(rec[need])} is missing next to {hits[0]} (--anomaly_weight={weight} needs it)")
+        out.append(rec)
+    return out
+
+
+def match_labels(subjects, spec):
+    """the label volume of every subject, matched by stem among ``list_inputs(spec)``; a subject without exactly one is refused by name"""
+    found = list_inputs(spec)
+    out = []
+    for s in subjects:
+        hits = [f for f in found if _stem(f) == _stem(s)]
+        if len(hits) != 1:
+            raise ValueError(f"{s}: {len(hits)} label volumes with the stem {_stem(s)} in --anomaly_labels={spec} (exactly one is needed)")
+        out.append(hits[0])
+    return out
+
+
+def anomaly(cfg, rank, local, world, dev):
+    """--mode=anomaly: every validation subject against the decoding of its healed codes, on the device from the scan to the scores."""
+    import csv
+    from synthanatomy_amd.metrics.anomaly import anomaly_map, average_precision, best_dice, dice_from_counts
+    files = list_inputs(cfg["validation_subjects"])
+    healed = find_healing_outputs(files, cfg["anomaly_codes"] or cfg["outputs_directory"], cfg["anomaly_weight"])      # host only: refusals come first
+    label_files = match_labels(files, cfg["anomaly_labels"]) if cfg["anomaly_labels"] is not None else None
+    sigma = _anomaly_sigma(cfg)
+    net = build_network(cfg, dev).eval()
+    path = check_for_checkpoints(cfg)
+    if path:
+        load_network_state(net, path)
+        log(rank, f"loaded {path}")
+    gen = torch.Generator(device=dev).manual_seed(cfg["seed"] + rank)
+    saver = None
+    if cfg["output_ext"] != ".npy":
+        from synthanatomy_amd.utils.vqvae import NiftiSaver, nifti_output_geometry
+        saver = NiftiSaver(cfg["output_ext"], cfg["output_dtype"], min(int(cfg.get("num_workers") or 0), 8))
+        canonical = bool(cfg.get("load_nii_canonical", True))
+    index = {f: k for k, f in enumerate(files)}
+    order = shard_for_rank(len(files), rank, world, shuffle=False, pad=False)
+    raw_cfg = dict(cfg, normalize=False)      # label volumes: the scans' reorientation and ROI, never their normalisation
+    rows = []
+    try:
+        with torch.no_grad():
+            for names, x, headers in _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev):
+                grids, weights = [], []
+                for n in names:
+                    h = healed[index[n]]
+                    codes = np.load(h["healed"]).astype(np.int64)
+                    if codes.min() < 0 or codes.max() >= net.n_embed:      # the check of --mode=decoding
+                        raise ValueError(f"{h['healed']}: code {int(codes.max())} is not a codebook entry (num_embeddings={net.n_embed})")
+                    grids.append(torch.from_numpy(codes))
+                    if cfg["anomaly_weight"] != "none":
+                        wgt = np.load(h["resampled" if cfg["anomaly_weight"] == "mask" else "nll"]).astype(np.float32)
+                        if wgt.shape != codes.shape:
+                            raise ValueError(f"{n}: the weight grid {wgt.shape} and the healed codes {codes.shape} differ in shape")
+                        weights.append(torch.from_numpy(wgt))
+                rec = net.decode_samples([torch.stack(grids).to(dev)]).float()
+                if rec.shape != x.shape:
+                    raise ValueError(f"{names[0]}: the healed codes decode to {tuple(rec.shape[2:])}, the scan is {tuple(x.shape[2:])} (--roi?)")
+                labels = None
+                if label_files is not None:
+                    labels = torch.stack([_load_volume(label_files[index[n]], raw_cfg, gen, dev).reshape(x.shape[1:]) for n in names])
+                amap, summ = anomaly_map(x, rec, torch.stack(weights).to(dev) if weights else None, sigma=sigma, residual=cfg["anomaly_residual"],
+                                         labels=labels, threshold=cfg["anomaly_threshold"], hist_max=cfg["anomaly_hist_max"])
+                if saver is None:
+                    for n, a_, r_ in zip(names, amap.cpu().numpy(), rec.cpu().numpy()):
+                        save_npy(a_[0], cfg["outputs_directory"], n, "anomaly_map", np.float32)
+                        save_npy(r_[0], cfg["outputs_directory"], n, "healed_reconstruction", np.float32)
+                else:
+                    saver.batch()
+                    for n, a_, r_, h in zip(names, amap, rec, headers):
+                        geom = nifti_output_geometry(h, cfg["roi"], canonical, a_.shape[-3:])
+                        saver.save(a_[0], _output_path(cfg, n, "anomaly_map"), *geom)
+                        saver.save(r_[0], _output_path(cfg, n, "healed_reconstruction"), *geom)
+                sums, maxs, hist = summ["sum"].cpu().numpy(), summ["max"].cpu().numpy(), summ["hist"].cpu().numpy()
+                counts = [summ[k].cpu().numpy() for k in ("tp", "fp", "fn")] if summ["tp"] is not None else None
+                for j, n in enumerate(names):
+                    row = {"subject": _stem(n), "sum": repr(float(sums[j])), "max": repr(float(maxs[j]))}
+                    if labels is not None:
+                        bd, bt = best_dice(hist[j, 0], hist[j, 1], summ["inv_bin"])
+                        row.update(dice="" if counts is None else repr(dice_from_counts(counts[0][j], counts[1][j], counts[2][j])),
+                                   best_dice=repr(bd), best_dice_threshold=repr(bt), average_precision=repr(average_precision(hist[j, 0], hist[j, 1])))
+                    rows.append(row)
+    finally:
+        if saver is not None:
+            saver.close()
+    fields = ["subject", "sum", "max"] + (["dice", "best_dice", "best_dice_threshold", "average_precision"] if label_files is not None else [])
+    with open(os.path.join(cfg["outputs_directory"], f"anomaly_scores_rank{rank}.csv"), "w", newline="") as f:
+        wr = csv.DictWriter(f, fieldnames=fields)
+        wr.writeheader()
+        wr.writerows(rows)
+    log(rank, f"anomaly done: {len(order)} subjects -> {cfg['outputs_directory']}")
+
+
 def run(argv):
     from synthanatomy_amd.runtime.ddp import init_distributed
     cfg = parse_flags(argv, DEFAULTS)
-    if cfg["mode"] not in ("training", "extracting", "decoding"):
-        raise ValueError(f"VQVAE mode unknown. Was given {cfg['mode']} but choices are ['training', 'extracting', 'decoding'].")
+    if cfg["mode"] not in MODES:
+        raise ValueError(f"VQVAE mode unknown. Was given {cfg['mode']} but choices are {MODES}.")
     _check_output_flags(cfg)
+    if cfg["mode"] == "anomaly":
+        _check_anomaly_flags(cfg)
     rank, local, world = init_distributed()
     cfg.update(rank=rank, local_rank=local, world_size=world)
     torch.manual_seed(cfg["seed"])
@@ -446,7 +620,7 @@ def run(argv):
         log(rank, "--deterministic: fixed-order reductions (csrc/deterministic.hip); slower than the default path")
     create_folder_structure(cfg)
     dev = torch.device("cuda", local)
-    (training if cfg["mode"] == "training" else inference)(cfg, rank, local, world, dev)
+    {"training": training, "anomaly": anomaly}.get(cfg["mode"], inference)(cfg, rank, local, world, dev)
 
 
 if __name__ == "__main__":

@@ -71,6 +71,17 @@ class EgressParams(Structure):
                 ("slope", ctypes.c_double), ("inter", ctypes.c_double)]
 
 
+# include/synthanatomy_hip.h: SA_ANOMALY_MAX_R, SA_ANOMALY_RESULT_WORDS.  One result record per volume, 64-bit words: [0] sum a (double), [1] max a (double
+# holding the float), [2], [3], [4] TP, FP, FN, [5..7] 0, [8 + 256 c + k] voxels of label class c in histogram bin k
+ANOMALY_MAX_R, ANOMALY_RESULT_WORDS = 24, 520
+
+
+class AnomalyParams(Structure):
+    """sa_anomaly_params (include/synthanatomy_hip.h): read on the host by sa_anomaly_map."""
+    _fields_ = [("B", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32), ("d", c_int32), ("h", c_int32), ("w", c_int32), ("residual", c_int32),
+                ("R", c_int32), ("has_threshold", c_int32), ("inv_bin", c_float), ("threshold", c_float), ("taps", c_float * (2 * ANOMALY_MAX_R + 1))]
+
+
 _SIGS = {
     "sa_abi_version": (c_int, []),
     "sa_last_error": (c_char_p, []),
@@ -123,6 +134,8 @@ _SIGS = {
     "sa_volume_ingest_workspace_bytes": (c_int64, []),
     "sa_volume_egress": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sa_volume_egress_workspace_bytes": (c_int64, []),
+    "sa_anomaly_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AnomalyParams), c_void_p, c_void_p, c_void_p]),
+    "sa_anomaly_map_workspace_bytes": (c_int64, [POINTER(AnomalyParams)]),
     "sa_bn_sums_ws_floats": (c_int64, [c_int]),
     "sa_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "sa_embed_sum": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p]),

@@ -1,0 +1,335 @@
+// Voxel-space anomaly map of a healed volume: sa_anomaly_map (include/synthanatomy_hip.h).  Per volume, with x the scan, r the decoded
+// healed codes and m an optional latent weight grid (the resampling mask or the NLL map of Performer.heal) on a grid f_D x f_H x f_W times coarser:
+//   e = |x - r|, max(x - r, 0) or max(r - x, 0);   u = m upsampled by nearest cell, zero outside the volume;
+//   w = u filtered with the separable (2R + 1)-tap Gaussian g ("same" size);   a = e w   (a = e without a weight grid)
+// and the summaries sum a, max a, a 256-bin histogram of a per label class and TP / FP / FN of [a >= t] against the label.
+//
+// One way to filter.  u is piecewise constant, so the filter along one axis is a banded operator from latent cells to voxels:
+//   A[p][c] = sum of the taps g[t], |t| <= R, whose voxel p + t lies in cell c (c f <= p + t < (c + 1) f),   w = A_D A_H A_W m.
+// A row has at most 2 ceil(R / f) + 1 entries that are not zero, and zero padding needs no code: a tap that leaves the volume lies in no cell.  A block
+// owns a tile of 8 x 32 (H x W) voxels and a run of 16 planes along D, one (h, w) column per thread.  It builds the three band tables for its tile in LDS
+// (entry = its taps added in ascending order), then walks the latent planes c_D its run can see: the plane's (cells_H x cells_W) neighbourhood goes
+// through LDS, A_W is applied for the tile's 32 columns, every thread applies its row of A_H, and the value is folded into the thread's 16 plane
+// accumulators with A_D.  Neither u nor w ever exists in memory; per voxel the kernel reads x, r and one optional label byte and writes a.
+// The x / r / label loads of all 16 planes are issued before the filter, which hides their latency.
+//
+// Summaries: every block leaves eight 64-bit words in the workspace -- sum a as fp64, max a, its bin-0 voxels of class 0 and of class 1, TP, FP, FN -- and
+// one block per volume adds them in a fixed order: no float atomics, and since a block never straddles volumes and the tiling depends on the volume's
+// shape only, a volume's map and summaries are bitwise the same alone or in any batch.  The counts every block contributes to (bin 0 of both classes:
+// most of a masked map is zero; TP / FP / FN) go that way too, counted in registers: thousands of blocks adding to ONE address serialise in L2 (measured:
+// 420 us instead of 75 for a 160 x 224 x 160 volume).  The other bins are LDS atomics per block, then 64-bit global atomic adds of the bins that are not
+// empty, 512 contiguous bytes per wave instruction.
+#include "sa_common.h"
+
+namespace sa {
+
+constexpr int AN_TW = 32, AN_TH = 8, AN_LD = 16;      // tile: W x H voxels (one column per thread), planes per run (16: 61 us against 79 for 8 on a
+                                                      // 160 x 224 x 160 volume, same call; 32 would leave 700 blocks for 256 CUs)
+constexpr int AN_THREADS = AN_TW * AN_TH;
+constexpr int AN_TAPS = 2 * SA_ANOMALY_MAX_R + 1;
+constexpr int AN_WORDS = SA_ANOMALY_RESULT_WORDS;
+constexpr int AN_PART = 8;                           // 64-bit words a block leaves in the workspace
+
+struct AnGeom {
+    int D, H, W, d, h, w, fD, fH, fW, R;
+    int tiles_h, tiles_w, chunks, nblk;      // blocks per volume
+    int nDm, nHm, nWm;                       // most latent cells a block's run / tile can see per axis (LDS strides)
+    int mode, has_t;
+    float inv_bin, t;
+};
+struct AnTaps { float g[AN_TAPS]; };
+
+// most cells of size f that L consecutive voxels can touch, capped by the cells there are
+static int an_span_cells(int L, int f, int cells) {
+    const int n = (L + f - 2) / f + 1;
+    return n < cells ? n : cells;
+}
+static int64_t an_align(int64_t v) { return (v + 15) & ~(int64_t)15; }
+// dynamic LDS in bytes: taps, A_D [nDm][LD], A_H [nHm][TH], A_W [nWm][TW], the latent plane's neighbourhood [nHm][nWm], its W-filtered rows [nHm][TW],
+// the 2 x 256 histogram, per wave one fp64, one fp32 and five counts
+static int64_t an_lds_floats(const AnGeom& g) {
+    return 64 + (int64_t)g.nDm * AN_LD + (int64_t)g.nHm * AN_TH + (int64_t)g.nWm * AN_TW + (int64_t)g.nHm * g.nWm + (int64_t)g.nHm * AN_TW;
+}
+static int64_t an_lds_bytes(const AnGeom& g) { return an_align(an_lds_floats(g) * 4) + 512 * 4 + 4 * 8 + 4 * 4 + 20 * 4; }
+
+__device__ __forceinline__ double an_wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float an_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t an_wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// A[p][c]: the taps of voxel p's window that fall into cell c, added in ascending order (at most min(f, 2R + 1) of them)
+__device__ __forceinline__ float an_band(const float* gs, int R, int p, int c, int f) {
+    const int lo = max(-R, c * f - p), hi = min(R, c * f + f - 1 - p);
+    float s = 0.f;
+    for (int t = lo; t <= hi; ++t) s += gs[t + R];
+    return s;
+}
+
+__global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ m,
+                                                                 const unsigned char* __restrict__ label, float* __restrict__ a_out, const AnGeom g,
+                                                                 const AnTaps taps, unsigned long long* __restrict__ part,
+                                                                 unsigned long long* __restrict__ results) {
+    extern __shared__ __attribute__((aligned(16))) char an_smem[];
+    float* gs = reinterpret_cast<float*>(an_smem);
+    float* AD = gs + 64;
+    float* AH = AD + g.nDm * AN_LD;
+    float* AW = AH + g.nHm * AN_TH;
+    float* ms = AW + g.nWm * AN_TW;
+    float* T1 = ms + g.nHm * g.nWm;
+    const int64_t nfl = 64 + (int64_t)g.nDm * AN_LD + (int64_t)g.nHm * AN_TH + (int64_t)g.nWm * AN_TW + (int64_t)g.nHm * g.nWm + (int64_t)g.nHm * AN_TW;
+    char* tail = an_smem + ((nfl * 4 + 15) & ~(int64_t)15);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(tail);               // [2][256]
+    double* red_s = reinterpret_cast<double*>(tail + 512 * 4);         // [4]
+    float* red_m = reinterpret_cast<float*>(tail + 512 * 4 + 4 * 8);   // [4]
+    uint32_t* red_c = reinterpret_cast<uint32_t*>(tail + 512 * 4 + 4 * 8 + 4 * 4);      // [5][4]
+
+    const int tid = threadIdx.x, wl = tid % AN_TW, hl = tid / AN_TW;
+    const int64_t b = blockIdx.y;
+    int blk = blockIdx.x;
+    const int tw = blk % g.tiles_w; blk /= g.tiles_w;
+    const int th = blk % g.tiles_h;
+    const int chunk = blk / g.tiles_h;
+    const int w0 = tw * AN_TW, h0 = th * AN_TH, p0 = chunk * AN_LD;
+    const int np = min(AN_LD, g.D - p0);
+    const bool valid = h0 + hl < g.H && w0 + wl < g.W;
+    const int64_t plane = (int64_t)g.H * g.W;
+    const int64_t base = (b * g.D + p0) * plane + (int64_t)(h0 + hl) * g.W + (w0 + wl);
+
+    hist[tid] = 0u;
+    hist[tid + AN_THREADS] = 0u;
+
+    // this thread's voxels: in flight while the weights are made
+    float xv[AN_LD], rv[AN_LD];
+    unsigned char lv[AN_LD];
+#pragma unroll
+    for (int k = 0; k < AN_LD; ++k) {
+        const bool ok = valid && k < np;
+        xv[k] = ok ? x[base + k * plane] : 0.f;
+        rv[k] = ok ? r[base + k * plane] : 0.f;
+        lv[k] = (ok && label) ? label[base + k * plane] : (unsigned char)0;
+    }
+
+    float wacc[AN_LD];
+#pragma unroll
+    for (int k = 0; k < AN_LD; ++k) wacc[k] = 0.f;
+    if (m) {
+        const int R = g.R;
+        for (int i = tid; i < 2 * R + 1; i += AN_THREADS) gs[i] = taps.g[i];
+        // the latent cells this run / tile can see: those that hold a voxel of [first - R, last + R] inside the volume
+        const int cD0 = max(p0 - R, 0) / g.fD, nD = min(g.D - 1, p0 + AN_LD - 1 + R) / g.fD - cD0 + 1;
+        const int cH0 = max(h0 - R, 0) / g.fH, nH = min(g.H - 1, h0 + AN_TH - 1 + R) / g.fH - cH0 + 1;
+        const int cW0 = max(w0 - R, 0) / g.fW, nW = min(g.W - 1, w0 + AN_TW - 1 + R) / g.fW - cW0 + 1;
+        __syncthreads();
+        for (int e = tid; e < nD * AN_LD; e += AN_THREADS) {
+            const int j = e / AN_LD, k = e % AN_LD;
+            AD[e] = p0 + k < g.D ? an_band(gs, R, p0 + k, cD0 + j, g.fD) : 0.f;
+        }
+        for (int e = tid; e < nH * AN_TH; e += AN_THREADS) {
+            const int j = e / AN_TH, k = e % AN_TH;
+            AH[e] = h0 + k < g.H ? an_band(gs, R, h0 + k, cH0 + j, g.fH) : 0.f;
+        }
+        for (int e = tid; e < nW * AN_TW; e += AN_THREADS) {
+            const int j = e / AN_TW, k = e % AN_TW;
+            AW[e] = w0 + k < g.W ? an_band(gs, R, w0 + k, cW0 + j, g.fW) : 0.f;
+        }
+        const float* mb = m + b * ((int64_t)g.d * g.h * g.w);
+        for (int j = 0; j < nD; ++j) {
+            // (cD0 + j < d, cH0 + ih < h, cW0 + iw < w by the construction of nD, nH, nW)
+            for (int e = tid; e < nH * nW; e += AN_THREADS) {
+                const int ih = e / nW, iw = e - ih * nW;
+                ms[ih * g.nWm + iw] = mb[((int64_t)(cD0 + j) * g.h + (cH0 + ih)) * g.w + (cW0 + iw)];
+            }
+            __syncthreads();      // (the first pass: the band tables too)
+            for (int e = tid; e < nH * AN_TW; e += AN_THREADS) {
+                const int ih = e / AN_TW, c = e % AN_TW;
+                float acc = 0.f;
+                for (int iw = 0; iw < nW; ++iw) acc = fmaf(AW[iw * AN_TW + c], ms[ih * g.nWm + iw], acc);
+                T1[e] = acc;
+            }
+            __syncthreads();
+            float s = 0.f;
+            for (int ih = 0; ih < nH; ++ih) s = fmaf(AH[ih * AN_TH + hl], T1[ih * AN_TW + wl], s);
+#pragma unroll
+            for (int k = 0; k < AN_LD; ++k) wacc[k] = fmaf(AD[j * AN_LD + k], s, wacc[k]);
+        }
+    } else {
+        __syncthreads();          // the histogram is clear
+    }
+
+    double bs = 0.0;
+    float bm = 0.f;
+    uint32_t cnt[5] = {0u, 0u, 0u, 0u, 0u};      // bin 0 of class 0, bin 0 of class 1, TP, FP, FN
+#pragma unroll
+    for (int k = 0; k < AN_LD; ++k) {
+        if (valid && k < np) {
+            const float dlt = xv[k] - rv[k];
+            const float e = g.mode == SA_ANOMALY_ABS ? fabsf(dlt) : g.mode == SA_ANOMALY_POSITIVE ? fmaxf(dlt, 0.f) : fmaxf(-dlt, 0.f);
+            const float a = m ? e * wacc[k] : e;
+            a_out[base + k * plane] = a;
+            bs += (double)a;
+            bm = fmaxf(bm, a);
+            const int bin = (int)fminf(a * g.inv_bin, 255.f);
+            const uint32_t cls = lv[k] != 0 ? 1u : 0u;
+            if (bin == 0) {
+                cnt[0] += cls ^ 1u;
+                cnt[1] += cls;
+            } else {
+                atomicAdd(&hist[cls * 256u + (uint32_t)bin], 1u);
+            }
+            if (g.has_t) {
+                const uint32_t pred = a >= g.t ? 1u : 0u;
+                cnt[2] += pred & cls;
+                cnt[3] += pred & (cls ^ 1u);
+                cnt[4] += (pred ^ 1u) & cls;
+            }
+        }
+    }
+    bs = an_wave_sum_f64(bs);
+    bm = an_wave_max(bm);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) cnt[q] = an_wave_sum_u32(cnt[q]);
+    unsigned long long* res = results + b * AN_WORDS;
+    if ((tid & 63) == 0) {
+        red_s[tid >> 6] = bs;
+        red_m[tid >> 6] = bm;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) red_c[q * 4 + (tid >> 6)] = cnt[q];
+    }
+    __syncthreads();
+    unsigned long long* pp = part + (b * g.nblk + blockIdx.x) * AN_PART;
+    if (tid == 0) {
+        pp[0] = (unsigned long long)__double_as_longlong((red_s[0] + red_s[1]) + (red_s[2] + red_s[3]));
+        pp[1] = (unsigned long long)__double_as_longlong((double)fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3])));
+    } else if (tid < 6) {
+        const uint32_t* c = red_c + (tid - 1) * 4;
+        pp[1 + tid] = (unsigned long long)c[0] + c[1] + c[2] + c[3];
+    }
+    for (int i = tid; i < 512; i += AN_THREADS) {      // (words 0 and 256 stay empty here: bin 0 travels through the workspace)
+        const uint32_t v = hist[i];
+        if (v) atomicAdd(res + 8 + i, (unsigned long long)v);
+    }
+}
+
+// results[b][0] = sum a, [1] = max a (both as doubles), [2..4] = TP, FP, FN, [8] and [8 + 256] = bin 0 of the two classes: one block per volume, lanes
+// and waves in a fixed order
+__global__ __launch_bounds__(256) void anomaly_finish_kernel(const unsigned long long* __restrict__ part, int nblk, unsigned long long* __restrict__ results) {
+    __shared__ double red_s[4], red_m[4];
+    __shared__ unsigned long long red_c[5][4];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const unsigned long long* pp = part + b * nblk * AN_PART;
+    double s = 0.0, mx = 0.0;
+    unsigned long long c[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    for (int i = tid; i < nblk; i += 256) {
+        s += __longlong_as_double((long long)pp[AN_PART * i]);
+        mx = fmax(mx, __longlong_as_double((long long)pp[AN_PART * i + 1]));
+#pragma unroll
+        for (int q = 0; q < 5; ++q) c[q] += pp[AN_PART * i + 2 + q];
+    }
+    s = an_wave_sum_f64(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmax(mx, __shfl_xor(mx, o, 64));
+#pragma unroll
+        for (int q = 0; q < 5; ++q) c[q] += __shfl_xor(c[q], o, 64);
+    }
+    if ((tid & 63) == 0) {
+        red_s[tid >> 6] = s;
+        red_m[tid >> 6] = mx;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) red_c[q][tid >> 6] = c[q];
+    }
+    __syncthreads();
+    unsigned long long* res = results + b * AN_WORDS;
+    if (tid == 0) {
+        res[0] = (unsigned long long)__double_as_longlong((red_s[0] + red_s[1]) + (red_s[2] + red_s[3]));
+        res[1] = (unsigned long long)__double_as_longlong(fmax(fmax(red_m[0], red_m[1]), fmax(red_m[2], red_m[3])));
+    } else if (tid < 6) {
+        const int q = tid - 1;
+        const unsigned long long v = red_c[q][0] + red_c[q][1] + red_c[q][2] + red_c[q][3];
+        res[q == 0 ? 8 : q == 1 ? 8 + 256 : q] = v;      // q = 2, 3, 4: TP, FP, FN sit in words 2, 3, 4
+    }
+}
+
+}  // namespace sa
+
+using namespace sa;
+
+namespace {
+
+// SA_EINVAL for what the rule refuses (a side that its latent side does not divide, R outside 0..24, a residual mode it does not know, inv_bin <= 0);
+// SA_EUNSUPPORTED for what this kernel does not cover (B > 65535, a volume of 2^31 voxels or more, a tile neighbourhood beyond 64 KiB of LDS)
+int an_plan(const sa_anomaly_params& P, bool weighted, AnGeom& g) {
+    if (P.B < 1 || P.D < 1 || P.H < 1 || P.W < 1) return SA_EINVAL;
+    if (P.residual != SA_ANOMALY_ABS && P.residual != SA_ANOMALY_POSITIVE && P.residual != SA_ANOMALY_NEGATIVE) return SA_EINVAL;
+    if (P.R < 0 || P.R > SA_ANOMALY_MAX_R) return SA_EINVAL;
+    if (!(P.inv_bin > 0.f) || P.inv_bin - P.inv_bin != 0.f) return SA_EINVAL;
+    if (P.has_threshold && P.threshold - P.threshold != 0.f) return SA_EINVAL;
+    g.D = P.D; g.H = P.H; g.W = P.W;
+    g.d = g.h = g.w = g.fD = g.fH = g.fW = 1;
+    if (weighted) {
+        if (P.d < 1 || P.h < 1 || P.w < 1 || P.D % P.d || P.H % P.h || P.W % P.w) return SA_EINVAL;
+        g.d = P.d; g.h = P.h; g.w = P.w;
+        g.fD = P.D / P.d; g.fH = P.H / P.h; g.fW = P.W / P.w;
+    }
+    g.R = P.R;
+    if (P.B > 65535) return SA_EUNSUPPORTED;
+    const int64_t vol = (int64_t)P.D * P.H * P.W;
+    if (vol >= 0x7fffffffll) return SA_EUNSUPPORTED;
+    g.tiles_h = (P.H + AN_TH - 1) / AN_TH;
+    g.tiles_w = (P.W + AN_TW - 1) / AN_TW;
+    g.chunks = (P.D + AN_LD - 1) / AN_LD;
+    const int64_t nblk = (int64_t)g.tiles_h * g.tiles_w * g.chunks;      // <= vol
+    g.nblk = (int)nblk;
+    g.nDm = weighted ? an_span_cells(AN_LD + 2 * P.R, g.fD, g.d) : 0;
+    g.nHm = weighted ? an_span_cells(AN_TH + 2 * P.R, g.fH, g.h) : 0;
+    g.nWm = weighted ? an_span_cells(AN_TW + 2 * P.R, g.fW, g.w) : 0;
+    if (an_lds_bytes(g) > 65536) return SA_EUNSUPPORTED;      // (R <= 24 keeps it below 44 KiB: 56 x 80 cells at f = 1)
+    g.mode = P.residual;
+    g.has_t = P.has_threshold != 0;
+    g.inv_bin = P.inv_bin;
+    g.t = P.threshold;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t sa_anomaly_map_workspace_bytes(const sa_anomaly_params* params) {
+    if (!params) return SA_EINVAL;
+    AnGeom g;
+    const int rc = an_plan(*params, params->d > 0, g);
+    return rc ? rc : (int64_t)params->B * g.nblk * AN_PART * 8;
+}
+
+extern "C" int sa_anomaly_map(const float* x, const float* r, const float* m, const unsigned char* label, float* a_out,
+                              const sa_anomaly_params* params, void* results, void* ws, void* stream) {
+    if (!x || !r || !a_out || !params || !results || !ws || (((uintptr_t)results) & 7u) != 0 || (((uintptr_t)ws) & 7u) != 0) return SA_EINVAL;
+    AnGeom g;
+    const int rc = an_plan(*params, m != nullptr, g);
+    if (rc) return rc;
+    AnTaps taps;
+    for (int i = 0; i < AN_TAPS; ++i) taps.g[i] = i < 2 * params->R + 1 ? params->taps[i] : 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = params->B;
+    if (hipMemsetAsync(results, 0, (size_t)B * AN_WORDS * 8, st) != hipSuccess) {
+        g_last_error = hipGetLastError();
+        return (int)g_last_error;
+    }
+    SA_LAUNCH(anomaly_map_kernel, dim3((unsigned)g.nblk, (unsigned)B), dim3(AN_THREADS), (size_t)an_lds_bytes(g), st, x, r, m, label, a_out, g, taps,
+              (unsigned long long*)ws, (unsigned long long*)results);
+    SA_CHECK_LAUNCH();
+    SA_LAUNCH(anomaly_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const unsigned long long*)ws, g.nblk, (unsigned long long*)results);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
