@@ -602,6 +602,34 @@ int sa_taps_unfold(const float *x, int dtype, void *xc, float *db, int N, int Di
 int sa_taps_fold(const float *p, const float *bias, float *out, int N, int Dc, int Hc, int Wc, int Do, int Ho, int Wo, int k, int stride, int pad, int dil,
                  int ld, void *stream);
 
+/* ---- the 2.5D LPIPS-alex perceptual term (csrc/lpips.hip) --------------------------------------------------------------
+ * Replaces, for PerceptualLoss / JukeboxPerceptualLoss / HartleyPerceptualLoss (reference src/losses/vqvae/vqvae.py:931-988 _calculate_fake_3d_loss:
+ * permute().contiguous().view(), the randperm gather, lpips.LPIPS.forward and their autograd), everything around the five convolutions, which
+ * are sa_conv_fprop launches with 2-D geometries (Di = Dm = Do = 1).  A view (0, 1, 2 = the reference's permutes (0,2,1,3,4), (0,3,1,2,4), (0,4,1,2,3))
+ * has n = D, H, W slices per volume of h x w = H x W, D x W, D x H pixels; slice id = b * n + a; slice_ids is a device list of S kept ids.
+ * sa_lpips_unfold     : cols [S, ho, wo, ld] (`dtype`) from the fp32 volume x [B, 1, D, H, W]: columns 0 .. 120 = the 11 x 11 / stride 4 / pad 2 taps
+ *                       (t = 11 ti + tj) of 2x - 1 (x when !normalize), 0 outside the image; columns 121 .. 129 = one-hot of the border class 3 cH + cW
+ *                       (c = 0 window inside, 1 it starts before the image, 2 it ends after it) so that the caller's weight matrix can undo the
+ *                       scaling layer's shift on padded taps exactly; the rest 0.  ho = (h - 7) / 4 + 1.  ld >= 130, rows a multiple of 16 bytes.
+ * sa_lpips_fold       : grad (fp32 volume, ACCUMULATED) += scale * sum over the <= 3 x 3 output positions covering each voxel of the kept slices of
+ *                       dcols [S, ho, wo, ld] fp32, in a fixed order; one thread per voxel, no atomics (the ids of one call must be distinct).
+ * sa_lpips_maxpool_fwd: y [S, Ho, Wo, C] = MaxPool2d(3, 2) of x [S, Hi, Wi, C] (channels-last, Ho = (Hi - 3) / 2 + 1), idx = window position
+ *                       3 kh + kw of the FIRST maximum in row-major order (one byte per output element).
+ * sa_lpips_maxpool_bwd: gx [S, Hi, Wi, C] = (addend + the gy of every window whose idx points here) * (mask > 0); addend / mask may be NULL;
+ *                       rows / columns that no window covers get addend alone.
+ * sa_lpips_head       : one tap: d[s] += mean_p sum_c w[c] (f0^ - f1^)^2 over f0, f1 [S, P, C], f^ = f / (sqrt(sum_c f^2) + 1e-10); g1 (may be NULL) =
+ *                       d (that term) / d f1 in `dtype`, times (f1 > 0) when relu_mask.  Where f1 is all zero the projection term is dropped (subgradient
+ *                       0 of the square root; upstream's autograd gives NaN there).  One block per slice, fixed-order reduction.  C <= 512.
+ * dtype: SA_F32 / SA_BF16 (else SA_EUNSUPPORTED).  SA_EINVAL: NULL operands, a view outside 0 .. 2, h or w < 7, non-positive extents, ld too small
+ * or misaligned, counts >= 2^31 - 256. */
+int sa_lpips_unfold(const float *x, int dtype, void *cols, const int32_t *slice_ids, int S, int view, int B, int D, int H, int W, int normalize, int ld,
+                    void *stream);
+int sa_lpips_fold(const float *dcols, float *grad, const int32_t *slice_ids, int S, int view, int B, int D, int H, int W, float scale, int ld, void *stream);
+int sa_lpips_maxpool_fwd(const void *x, int dtype, void *y, void *idx, int S, int Hi, int Wi, int C, void *stream);
+int sa_lpips_maxpool_bwd(const void *gy, const void *idx, const void *addend, const void *mask, int dtype, void *gx, int S, int Hi, int Wi, int C,
+                         void *stream);
+int sa_lpips_head(const void *f0, const void *f1, int dtype, const float *w, int S, int P, int C, float *d, void *g1, int relu_mask, void *stream);
+
 /* ---- FAVOR+ global heads with the feature maps recomputed on chip (csrc/favor_fused.hip; throughput mode) ------------------------------------
  * Replaces, for performer_pytorch.FastAttention / softmax_kernel / causal_linear_attention (reference src/networks/transformers/performer.py:194-219
  * delegates to them), the chain sa_favor_project* -> sa_favor_features_fwd -> sa_favor_scan_a_norm (forward) and sa_favor_dden -> sa_favor_scan_b_cum x2 ->

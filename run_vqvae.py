@@ -7,7 +7,9 @@
 MONAI/ignite/fire/deepspeed are not on the target, so the loop is a minimal in-house one: Adam + per-iteration ExponentialLR
 (run_vqvae.py:82-91,162), losses "mse", "jukebox" (spectral), "spectral" / "hartley" / "wavegan" (FFT amplitude + phase, weighted Hartley and
 spectral convergence + log magnitude; their factors are not scheduled, as upstream) and "baur" (L1 + L2 + image-gradient difference, its factor scheduled per epoch
-by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_factor_value; the LPIPS family is out of scope), optional adversarial component
+by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_factor_value) and "perceptual" / "jukebox_perceptual" / "hartley_perceptual"
+(2.5D LPIPS-alex on HIP; they need --perceptual_weights=<file in the lpips.LPIPS(net='alex') state-dict layout, see tools/make_lpips_weights.py |
+random:seed>, nothing is downloaded), optional adversarial component
 (src/engines/trainer.py semantics incl. the adaptive weight; criteria vanilla / hinge / least_square), checkpoints with the reference's keys
 (network, optimizer, lr_scheduler, trainer, d_*) restored on resume, uint16 ``.npy`` code files.
 Inputs: ``.npy`` volumes, single-file NIfTI-1 volumes (``.nii`` / ``.nii.gz``: read with the standard library, then converted, reoriented to the
@@ -67,7 +69,7 @@ DEFAULTS = dict(
     downsample_parameters=((4, 2, 1, 1),) * 3, upsample_parameters=((4, 2, 1, 0, 1),) * 3, no_res_layers=3, no_channels=256, codebook_type="ema",
     num_embeddings=(256,), embedding_dim=(256,), embedding_init=("normal",), commitment_cost=(0.25,), decay=(0.99,), decay_warmup=None,
     max_decay_epochs=50, norm=None, dropout=0.0, act="RELU", output_act=None, evaluation_checkpoint="recent", load_nii_canonical=True,
-    output_ext=".npy", output_dtype="float32",
+    output_ext=".npy", output_dtype="float32", perceptual_weights=None,
     anomaly_codes=None, anomaly_weight="mask", anomaly_sigma=None, anomaly_residual="abs", anomaly_threshold=None, anomaly_hist_max=1.0, anomaly_labels=None,
 )
 MODES = ["training", "extracting", "decoding", "anomaly"]
@@ -87,6 +89,19 @@ def _check_output_flags(cfg):
     if ext != ".npy" and n_aug > 0:
         raise ValueError(f"--output_ext={ext} with --no_augmented_extractions={n_aug}: augmented extractions are not on the source grid and exist for "
                          "their codes; leave --output_ext at .npy")
+
+
+def _check_perceptual_flags(cfg):
+    """--loss=*perceptual needs --perceptual_weights: the file is read and checked by key and shape here, on the host, before anything touches the device
+    (wrong weights are refused by name, never replaced).  Returns the validated state dict, or None for every other loss."""
+    if not str(cfg["loss"]).endswith("perceptual"):
+        return None
+    spec = cfg.get("perceptual_weights")
+    if not spec:
+        raise ValueError(f"--loss={cfg['loss']} needs --perceptual_weights=<file | random:seed>: a torch.save'd dict in the key layout of "
+                         "lpips.LPIPS(net='alex').state_dict() (tools/make_lpips_weights.py merges the two upstream files; nothing is downloaded)")
+    from synthanatomy_amd.losses.lpips import load_weights
+    return load_weights(str(spec))
 
 
 def _output_path(cfg, filename, postfix):
@@ -274,8 +289,13 @@ def training(cfg, rank, local, world, dev):
     from synthanatomy_amd.losses.vqvae import gdl_factor_schedule, get_vqvae_loss
     from synthanatomy_amd.runtime.ddp import GradReducer
     from synthanatomy_amd.runtime.optim import ExponentialLR, FlatParams, FusedAdam, TrainerState
-    loss_fn = get_vqvae_loss(cfg)
+    loss_fn = get_vqvae_loss(dict(cfg, perceptual_weights=cfg.get("perceptual_state") or cfg.get("perceptual_weights")))
     baur = cfg["loss"] == "baur"      # gdl_factor scheduled at every finished epoch (src/losses/vqvae/configure.py:56-76)
+    perceptual = hasattr(loss_fn, "set_step")      # the LPIPS family: frozen weights as buffers on the device, slice draw keyed on the global iteration
+    if perceptual:
+        loss_fn.to(dev)
+        if str(cfg.get("perceptual_weights")).startswith("random:"):
+            log(rank, f"--perceptual_weights={cfg['perceptual_weights']}: seeded STAND-IN weights (tests, smoke runs, benchmarks): the perceptual term measures nothing")
     net = build_network(cfg, dev).train()
     flat = FlatParams(net.parameters())
     red = GradReducer(flat)
@@ -344,6 +364,8 @@ def training(cfg, rank, local, world, dev):
         else:
             batches = _batches(files, order, cfg["batch_size"], cfg, gen, dev)
         for names, x, *noise_seed in batches:
+            if perceptual:
+                loss_fn.set_step(state.iteration * world + rank)
             if trainer is not None:
                 res = trainer.iteration(x, x, epoch + 1)      # ignite's state.epoch is 1 during the first epoch (trainer.py:176)
                 loss = res["loss"]
@@ -361,6 +383,8 @@ def training(cfg, rank, local, world, dev):
                 extra = f" g_loss {float(res['g_loss']):.6f} d_loss {float(res['d_loss']):.6f} adv_weight {float(res['adversarial_weight']):.4f}" if res else ""
                 if baur:
                     extra += f" gdl_factor {loss_fn.get_gdl_factor():.6g}"
+                if perceptual:
+                    extra += "".join(f" {k} {float(v):.6g}" for k, v in loss_fn.get_summaries()["scalar"].items() if k.startswith("Loss-Perceptual_"))
                 if augmenting:
                     extra += f" input {'x'.join(str(n) for n in x.shape[2:])} noise_seed {noise_seed[0]:#018x}"
                 log(rank, f"epoch {epoch} it {state.iteration} loss {loss.item():.6f}{extra} perplexity {net.get_perplexity()[0].item():.2f} lr {opt.lr:.3e}")
@@ -608,6 +632,7 @@ def run(argv):
     _check_output_flags(cfg)
     if cfg["mode"] == "anomaly":
         _check_anomaly_flags(cfg)
+    cfg["perceptual_state"] = _check_perceptual_flags(cfg) if cfg["mode"] == "training" else None
     rank, local, world = init_distributed()
     cfg.update(rank=rank, local_rank=local, world_size=world)
     torch.manual_seed(cfg["seed"])

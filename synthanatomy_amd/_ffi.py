@@ -208,6 +208,11 @@ _SIGS = {
     "sa_convt1_im2col": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sa_taps_unfold": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),
     "sa_taps_fold": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),
+    "sa_lpips_unfold": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "sa_lpips_fold": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float, c_int, c_void_p]),
+    "sa_lpips_maxpool_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "sa_lpips_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "sa_lpips_head": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "sa_convt1_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sa_favor_fused_state_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "sa_favor_fused_proj_tiles": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

@@ -68,7 +68,10 @@ static int conv_fprop_impl(const sa_conv_geom* g, int ncls, int dtype, const voi
     {
         const int sz = dtype == SA_F32 ? 4 : 2;
         const uint64_t ib = (uint64_t)g->N * g->Di * g->Hi * g->Wi * g->Cin * sz, wb = (uint64_t)g->CoutPad * g->Kpad * sz;
-        const bool fits = ib < 0xfffffff0ull - 4096 && wb < 0xfffffff0ull && !dbg(SA_DBG_NO_DMA);
+        // the LDS-DMA mainloops keep a row's tap validity as FOUR bits per axis: a geometry with more than four taps on an axis (the 5 x 5 convolution of
+        // the LPIPS stack, KT = {1, 5, 5}; no 3-D layer has one: conv_plan.MAX_KERNEL = 4) takes the register-staged mainloop, which bounds-checks every tap
+        const bool taps4 = g->KT[0] <= 4 && g->KT[1] <= 4 && g->KT[2] <= 4;
+        const bool fits = ib < 0xfffffff0ull - 4096 && wb < 0xfffffff0ull && !dbg(SA_DBG_NO_DMA) && taps4;
         a.in_bytes = fits ? (uint32_t)ib : 0u;
         a.w_bytes = fits ? (uint32_t)wb : 0u;
     }

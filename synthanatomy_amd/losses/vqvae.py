@@ -374,8 +374,186 @@ class WaveGANLoss(_FourierLoss):
         return self.get_fft_factor()
 
 
-# of the reference's src/losses/vqvae/utils.py list; the LPIPS family (perceptual, jukebox_perceptual, hartley_perceptual, baseline) is out of scope
-VQVAE_LOSSES = ("baur", "mse", "jukebox", "spectral", "hartley", "wavegan")
+_FAKE_3D_VIEW = {2: 0, 3: 1, 4: 2}      # fake_3d_axis entry -> view id of sa_lpips_unfold (the reference's permutes (0,2,1,3,4), (0,3,1,2,4), (0,4,1,2,3))
+
+
+class _PerceptualLoss(torch.nn.Module):
+    """What ``PerceptualLoss``, ``JukeboxPerceptualLoss`` and ``HartleyPerceptualLoss`` share: the 2.5D LPIPS-alex term (losses/lpips.py, csrc/lpips.hip;
+    DESIGN.md section 7.12), the pixel term and the commitment terms.  Beyond upstream's constructor arguments: ``perceptual_weights`` (a validated
+    LPIPS-alex state dict, losses.lpips.load_weights), ``compute_dtype`` (float32 = parity mode, bfloat16 = throughput mode) and ``seed`` (the slice
+    draw is keyed on (seed, step, view); the training loop calls :meth:`set_step` with the global iteration)."""
+
+    def __init__(self, dimensions: int, include_pixel_loss: bool = True, is_fake_3d: bool = True, drop_ratio: float = 0.0,
+                 fake_3d_axis=(2, 3, 4), lpips_kwargs: Dict = None, lpips_normalize: bool = True, *, perceptual_weights: Dict = None,
+                 compute_dtype: torch.dtype = torch.float32, seed: int = 0):
+        super().__init__()
+        from . import lpips
+        name = type(self).__name__
+        if dimensions != 3:
+            raise NotImplementedError(f"{name}: only dimensions=3 ([B, 1, D, H, W] volumes, the 2.5D approach) has a HIP path; got dimensions={dimensions}")
+        if not is_fake_3d:
+            raise NotImplementedError(f"{name}: is_fake_3d=False (a true 3D perceptual loss) is not implemented, as upstream")
+        if lpips_kwargs is not None:
+            want = {k: v for k, v in lpips.DEFAULT_LPIPS_KWARGS.items() if k != "verbose"}
+            if any(k not in want or want[k] != v for k, v in dict(lpips_kwargs).items() if k != "verbose"):
+                raise NotImplementedError(f"{name}: only the default lpips_kwargs (net='alex', version='0.1', lpips=True, spatial=False, pnet_tune=False) "
+                                          f"have a HIP path; got lpips_kwargs={lpips_kwargs}")
+        if isinstance(drop_ratio, bool) or not isinstance(drop_ratio, (int, float)) or not 0 <= drop_ratio < 1:
+            raise ValueError(f"{name}: drop_ratio must lie in [0, 1); got drop_ratio={drop_ratio}")
+        axes = tuple(fake_3d_axis)
+        if not axes or any(a not in _FAKE_3D_VIEW for a in axes):
+            raise ValueError(f"{name}: fake_3d_axis must name axes among (2, 3, 4); got fake_3d_axis={fake_3d_axis}")
+        if perceptual_weights is None:
+            raise ValueError(f"{name}: perceptual_weights is required (this build downloads nothing): losses.lpips.load_weights(<file> | 'random:<seed>')")
+        self.dimensions, self.include_pixel_loss = dimensions, include_pixel_loss
+        self.lpips_kwargs = dict(lpips.DEFAULT_LPIPS_KWARGS)
+        self.fake_3D_views = [_FAKE_3D_VIEW[a] for a in (2, 3, 4) if a in axes]      # (upstream's order: by axis, whatever the tuple's order)
+        self.keep_ratio = 1 - drop_ratio
+        self.lpips_normalize = bool(lpips_normalize)
+        self.perceptual_function = lpips.LpipsAlex(perceptual_weights, compute_dtype)
+        self.perceptual_factor = 0.001
+        self.seed, self.step = int(seed), 0
+        self.chunk_slices = None           # None: from the workspace cap (tests halve it)
+        self.summaries: Dict = {"scalar": {}}
+
+    def set_step(self, step: int) -> int:
+        """the global training iteration: with the seed and the view it keys the slice draw, so a resumed run reproduces it"""
+        self.step = int(step)
+        return self.step
+
+    def _n_keep(self, n_slices: int) -> int:
+        return int(n_slices * self.keep_ratio)
+
+    def _check(self, y_pred: torch.Tensor, y: torch.Tensor):
+        from . import lpips
+        name = type(self).__name__
+        if y_pred.dim() != 5:
+            raise ValueError(f"{name} needs [B, 1, D, H, W] volumes; got {tuple(y_pred.shape)}")
+        if tuple(y.shape) != tuple(y_pred.shape):
+            raise ValueError(f"{name}: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
+        if y_pred.shape[1] != 1:
+            raise NotImplementedError(f"{name}: C = 1 only (the single channel broadcasts to LPIPS' three); got C={y_pred.shape[1]}")
+        B, _, D, H, W = y_pred.shape
+        for v in self.fake_3D_views:
+            n, sides = ((D, (H, W)), (H, (D, W)), (W, (D, H)))[v]
+            if min(sides) < lpips.MIN_SIDE:
+                raise ValueError(f"{name}: view {v} has slices of {sides[0]} x {sides[1]}; every slice side must be >= {lpips.MIN_SIDE} (the smallest for which "
+                                 f"AlexNet's second pool still has an output); got a volume of {D} x {H} x {W}")
+            if self._n_keep(B * n) < 1:
+                raise ValueError(f"{name}: drop_ratio={1 - self.keep_ratio:g} keeps 0 of the {B * n} slices of view {v}")
+
+    def _perceptual(self, y_pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """the sum of the per-view terms (differentiable to y_pred), summaries written"""
+        from . import lpips
+        self._check(y_pred, y)
+        B, _, D, H, W = y_pred.shape
+        ids = []
+        for v in self.fake_3D_views:          # every refusal above comes before the first launch; the lists are small int32 uploads
+            n = B * (D, H, W)[v]
+            ids.append(torch.from_numpy(lpips.draw_slices(self.seed, self.step, v, n, self._n_keep(n))).to(y_pred.device))
+        total, *terms = lpips.PerceptualFn.apply(y_pred, y, self.perceptual_function, tuple(self.fake_3D_views), ids, float(self.perceptual_factor),
+                                                 self.lpips_normalize, self.chunk_slices)
+        for idx, t in enumerate(terms):
+            self.summaries["scalar"][f"Loss-Perceptual_{idx}-Reconstruction"] = t.detach()
+        self.summaries["scalar"]["Auxiliary-Perceptual_Factor"] = self.perceptual_factor
+        return total
+
+    def _tail(self, loss, y_pred, y, network_output):
+        if self.include_pixel_loss:
+            l2 = hip_mse(y_pred, y)
+            self.summaries["scalar"]["Loss-MSE-Reconstruction"] = l2.detach()
+            loss = loss + l2
+        for idx, ql in enumerate(network_output["quantization_losses"]):
+            ql = ql.float()
+            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
+            loss = loss + ql
+        return loss
+
+    def _spectral(self, y_pred, y):
+        return None
+
+    def forward(self, network_output: Dict[str, List[torch.Tensor]], y: torch.Tensor) -> torch.Tensor:
+        y = y.float()
+        y_pred = network_output["reconstruction"][0].float()
+        self._check(y_pred, y)
+        spec = self._spectral(y_pred, y)
+        p = self._perceptual(y_pred, y)
+        return self._tail(p if spec is None else spec + p, y_pred, y, network_output)
+
+    def get_summaries(self):
+        return self.summaries
+
+    def get_perceptual_factor(self) -> float:
+        return self.perceptual_factor
+
+    def set_perceptual_factor(self, perceptual_factor: float) -> float:
+        self.perceptual_factor = perceptual_factor
+        return self.get_perceptual_factor()
+
+
+class PerceptualLoss(_PerceptualLoss):
+    """``PerceptualLoss(dimensions=3)`` of the reference (src/losses/vqvae/vqvae.py:774-1000, ``--loss=perceptual``): ``sum over the 2.5D views of
+    perceptual_factor * mean LPIPS(y slices, pred slices) + mse(pred, y) + sum(quantization_losses)``.  Same constructor arguments, ``summaries`` keys
+    and ``get/set_perceptual_factor`` as upstream."""
+
+
+class JukeboxPerceptualLoss(_PerceptualLoss):
+    """``JukeboxPerceptualLoss(dimensions=3)`` of the reference (src/losses/vqvae/vqvae.py:1003-1285, ``--loss=jukebox_perceptual``, the loss of the
+    published training recipe): :class:`JukeboxLoss`' spectral term + the perceptual term + pixel and commitment terms."""
+
+    def __init__(self, dimensions: int, include_pixel_loss: bool = True, is_fake_3d: bool = True, drop_ratio: float = 0.0, fake_3d_axis=(2, 3, 4),
+                 lpips_kwargs: Dict = None, lpips_normalize: bool = True, fft_kwargs: Dict = None, **kw):
+        super().__init__(dimensions, include_pixel_loss, is_fake_3d, drop_ratio, fake_3d_axis, lpips_kwargs, lpips_normalize, **kw)
+        self._jukebox = JukeboxLoss(dimensions=dimensions, include_pixel_loss=False, fft_kwargs=fft_kwargs)
+        self.fft_kwargs = self._jukebox.fft_kwargs
+
+    @property
+    def fft_factor(self) -> float:
+        return self._jukebox.fft_factor
+
+    def _spectral(self, y_pred, y):
+        spec = self._jukebox({"reconstruction": [y_pred], "quantization_losses": []}, y)
+        self.summaries["scalar"]["Loss-Spectral-Reconstruction"] = spec.detach()
+        self.summaries["scalar"]["Auxiliary-FFT_Factor"] = self._jukebox.fft_factor
+        return spec
+
+    def get_fft_factor(self) -> float:
+        return self._jukebox.get_fft_factor()
+
+    def set_fft_factor(self, fft_factor: float) -> float:
+        return self._jukebox.set_fft_factor(fft_factor)
+
+
+class HartleyPerceptualLoss(_PerceptualLoss):
+    """``HartleyPerceptualLoss(dimensions=3)`` of the reference (src/losses/vqvae/vqvae.py:1288-1645, ``--loss=hartley_perceptual``): :class:`HartleyLoss`'
+    weighted Hartley term (:class:`_FourierFn`) + the perceptual term + pixel and commitment terms."""
+
+    def __init__(self, dimensions: int, include_pixel_loss: bool = True, is_fake_3d: bool = True, drop_ratio: float = 0.0, fake_3d_axis=(2, 3, 4),
+                 lpips_kwargs: Dict = None, lpips_normalize: bool = True, fft_kwargs: Dict = None, prioritise_high_frequency: bool = True, **kw):
+        super().__init__(dimensions, include_pixel_loss, is_fake_3d, drop_ratio, fake_3d_axis, lpips_kwargs, lpips_normalize, **kw)
+        self._hartley = HartleyLoss(dimensions, include_pixel_loss=False, fft_kwargs=fft_kwargs, prioritise_high_frequency=prioritise_high_frequency)
+        self.fft_kwargs, self.prioritise_high_frequency = self._hartley.fft_kwargs, prioritise_high_frequency
+
+    @property
+    def fht_factor(self) -> float:
+        return self._hartley.fht_factor
+
+    def _spectral(self, y_pred, y):
+        spec = self._hartley({"reconstruction": [y_pred], "quantization_losses": []}, y)
+        self.summaries["scalar"]["Auxiliary-Hartley_Factor"] = self._hartley.fht_factor
+        self.summaries["scalar"]["Loss-Hartley-Reconstruction"] = spec.detach()
+        return spec
+
+    def get_fht_factor(self) -> float:
+        return self._hartley.get_fht_factor()
+
+    def set_fht_factor(self, fht_factor: float) -> float:
+        return self._hartley.set_fht_factor(fht_factor)
+
+
+# of the reference's src/losses/vqvae/utils.py list; the LPIPS family needs --perceptual_weights (this build downloads nothing); "baseline" (SqueezeNet) is out of scope
+VQVAE_LOSSES = ("baur", "mse", "jukebox", "spectral", "hartley", "wavegan", "perceptual", "jukebox_perceptual", "hartley_perceptual")
+_PERCEPTUAL_LOSSES = {"perceptual": PerceptualLoss, "jukebox_perceptual": JukeboxPerceptualLoss, "hartley_perceptual": HartleyPerceptualLoss}
 
 
 def get_vqvae_loss(config: dict) -> torch.nn.Module:
@@ -392,4 +570,14 @@ def get_vqvae_loss(config: dict) -> torch.nn.Module:
         return HartleyLoss(dimensions=3)
     if config["loss"] == "wavegan":
         return WaveGANLoss(dimensions=3)
-    raise ValueError(f"Loss function unknown. Was given {config['loss']} but choices are {list(VQVAE_LOSSES)}.")
+    if config["loss"] in _PERCEPTUAL_LOSSES and config.get("perceptual_weights"):
+        # drop_ratio 0.5 as src/losses/vqvae/configure.py:40-45; the weights come from --perceptual_weights (host only, refused by name when wrong)
+        from . import lpips
+        weights = config["perceptual_weights"]
+        if not isinstance(weights, dict):
+            weights = lpips.load_weights(weights)
+        dtype = config.get("compute_dtype") or (torch.bfloat16 if config.get("amp") else torch.float32)
+        return _PERCEPTUAL_LOSSES[config["loss"]](dimensions=3, drop_ratio=0.5, perceptual_weights=weights, compute_dtype=dtype,
+                                                  seed=int(config.get("seed") or 0))
+    hint = " The LPIPS family needs --perceptual_weights=<file | random:seed>." if config["loss"] in _PERCEPTUAL_LOSSES else ""
+    raise ValueError(f"Loss function unknown. Was given {config['loss']} but choices are {list(VQVAE_LOSSES)}.{hint}")
