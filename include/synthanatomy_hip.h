@@ -630,6 +630,32 @@ int sa_lpips_maxpool_bwd(const void *gy, const void *idx, const void *addend, co
                          void *stream);
 int sa_lpips_head(const void *f0, const void *f1, int dtype, const float *w, int S, int P, int C, float *d, void *g1, int relu_mask, void *stream);
 
+/* ---- the ends and the pools of the LPIPS-squeeze chain (csrc/lpips_squeeze.hip) ----------------------------------------
+ * Replaces, for BaselineLoss (reference src/losses/vqvae/vqvae.py:1706-1777 _calculate_perceptual_loss: permute().contiguous().view(), the randperm
+ * gather, lpips.LPIPS(net="squeeze").forward and their autograd) and for lpips_kwargs net="squeeze" of the three perceptual classes, everything
+ * around the Fire modules, which are sa_conv_fprop launches with 2-D geometries, and the seven taps, which are sa_lpips_head launches.  Views,
+ * slice ids and channels-last layouts as in the section above.
+ * sa_lpips_squeeze_conv1_fwd: y [S, ho, wo, 64] (`dtype`) = ReLU(bias + sum_t w[t][c] u(2 oh + ti, 2 ow + tj)), t = 3 ti + tj, u = 2x - 1 (x when
+ *                             !normalize) read from the fp32 volume x [B, 1, D, H, W]; ho = (h - 3) / 2 + 1, no padding.  w [9][64] and bias [64] fp32 are
+ *                             the caller's fold of the scaling layer into features.0 (exact: no window leaves the image).  A slice id outside the view
+ *                             reads zeros.
+ * sa_lpips_squeeze_conv1_bwd: grad (fp32 volume, ACCUMULATED) += scale * sum over the <= 2 x 2 positions covering each voxel of the kept slices and
+ *                             the 64 channels of gy * (mask > 0) * w, in a fixed order; gy, mask [S, ho, wo, 64] (`dtype`), mask (the tap; may be NULL);
+ *                             one thread per voxel, no atomics (the ids of one call must be distinct).
+ * sa_lpips_maxpool_ceil_fwd : y [S, Ho, Wo, C] = MaxPool2d(3, 2, ceil_mode=True) of x [S, Hi, Wi, C]: Ho = ceil((Hi - 3) / 2) + 1, minus one if the last
+ *                             window would start outside the map; windows are clipped to the map; idx = position 3 kh + kw IN THE FULL WINDOW of the
+ *                             FIRST maximum in row-major order (one byte per output element).
+ * sa_lpips_maxpool_ceil_bwd : gx [S, Hi, Wi, C] = (addend + the gy of every window whose idx points here) * (mask > 0); addend / mask may be NULL.
+ * dtype: SA_F32 / SA_BF16 (else SA_EUNSUPPORTED).  SA_EINVAL: NULL operands (but mask / addend), a view outside 0 .. 2, h or w < 3 (conv1), Hi or
+ * Wi < 2 (pools), non-positive extents, counts >= 2^31 - 256. */
+int sa_lpips_squeeze_conv1_fwd(const float *x, int dtype, const float *w, const float *bias, void *y, const int32_t *slice_ids, int S, int view, int B,
+                               int D, int H, int W, int normalize, void *stream);
+int sa_lpips_squeeze_conv1_bwd(const void *gy, const void *mask, int dtype, const float *w, float *grad, const int32_t *slice_ids, int S, int view, int B,
+                               int D, int H, int W, float scale, void *stream);
+int sa_lpips_maxpool_ceil_fwd(const void *x, int dtype, void *y, void *idx, int S, int Hi, int Wi, int C, void *stream);
+int sa_lpips_maxpool_ceil_bwd(const void *gy, const void *idx, const void *addend, const void *mask, int dtype, void *gx, int S, int Hi, int Wi, int C,
+                              void *stream);
+
 /* ---- FAVOR+ global heads with the feature maps recomputed on chip (csrc/favor_fused.hip; throughput mode) ------------------------------------
  * Replaces, for performer_pytorch.FastAttention / softmax_kernel / causal_linear_attention (reference src/networks/transformers/performer.py:194-219
  * delegates to them), the chain sa_favor_project* -> sa_favor_features_fwd -> sa_favor_scan_a_norm (forward) and sa_favor_dden -> sa_favor_scan_b_cum x2 ->

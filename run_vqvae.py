@@ -9,7 +9,8 @@ MONAI/ignite/fire/deepspeed are not on the target, so the loop is a minimal in-h
 spectral convergence + log magnitude; their factors are not scheduled, as upstream) and "baur" (L1 + L2 + image-gradient difference, its factor scheduled per epoch
 by --initial_factor_value / --initial_factor_steps / --max_factor_steps / --max_factor_value) and "perceptual" / "jukebox_perceptual" / "hartley_perceptual"
 (2.5D LPIPS-alex on HIP; they need --perceptual_weights=<file in the lpips.LPIPS(net='alex') state-dict layout, see tools/make_lpips_weights.py |
-random:seed>, nothing is downloaded), optional adversarial component
+random:seed>, nothing is downloaded) and "baseline" (L1 + five-axis FFT amplitude + three-plane LPIPS-squeeze; it needs --perceptual_weights in the
+lpips.LPIPS(net='squeeze') layout, tools/make_lpips_weights.py --net=squeeze), optional adversarial component
 (src/engines/trainer.py semantics incl. the adaptive weight; criteria vanilla / hinge / least_square), checkpoints with the reference's keys
 (network, optimizer, lr_scheduler, trainer, d_*) restored on resume, uint16 ``.npy`` code files.
 Inputs: ``.npy`` volumes, single-file NIfTI-1 volumes (``.nii`` / ``.nii.gz``: read with the standard library, then converted, reoriented to the
@@ -92,16 +93,18 @@ def _check_output_flags(cfg):
 
 
 def _check_perceptual_flags(cfg):
-    """--loss=*perceptual needs --perceptual_weights: the file is read and checked by key and shape here, on the host, before anything touches the device
-    (wrong weights are refused by name, never replaced).  Returns the validated state dict, or None for every other loss."""
-    if not str(cfg["loss"]).endswith("perceptual"):
+    """--loss=*perceptual (LPIPS-alex) and --loss=baseline (LPIPS-squeeze) need --perceptual_weights: the file is read and checked by key and shape here, on
+    the host, before anything touches the device (wrong weights, the other network's included, are refused by name, never replaced).  Returns the validated
+    state dict, or None for every other loss."""
+    if not str(cfg["loss"]).endswith("perceptual") and cfg["loss"] != "baseline":
         return None
+    net = "squeeze" if cfg["loss"] == "baseline" else "alex"
     spec = cfg.get("perceptual_weights")
     if not spec:
         raise ValueError(f"--loss={cfg['loss']} needs --perceptual_weights=<file | random:seed>: a torch.save'd dict in the key layout of "
-                         "lpips.LPIPS(net='alex').state_dict() (tools/make_lpips_weights.py merges the two upstream files; nothing is downloaded)")
+                         f"lpips.LPIPS(net='{net}').state_dict() (tools/make_lpips_weights.py merges the two upstream files; nothing is downloaded)")
     from synthanatomy_amd.losses.lpips import load_weights
-    return load_weights(str(spec))
+    return load_weights(str(spec), net=net)
 
 
 def _output_path(cfg, filename, postfix):
@@ -384,7 +387,7 @@ def training(cfg, rank, local, world, dev):
                 if baur:
                     extra += f" gdl_factor {loss_fn.get_gdl_factor():.6g}"
                 if perceptual:
-                    extra += "".join(f" {k} {float(v):.6g}" for k, v in loss_fn.get_summaries()["scalar"].items() if k.startswith("Loss-Perceptual_"))
+                    extra += "".join(f" {k} {float(v):.6g}" for k, v in loss_fn.get_summaries()["scalar"].items() if k.startswith("Loss-" if cfg["loss"] == "baseline" else "Loss-Perceptual_"))
                 if augmenting:
                     extra += f" input {'x'.join(str(n) for n in x.shape[2:])} noise_seed {noise_seed[0]:#018x}"
                 log(rank, f"epoch {epoch} it {state.iteration} loss {loss.item():.6f}{extra} perplexity {net.get_perplexity()[0].item():.2f} lr {opt.lr:.3e}")

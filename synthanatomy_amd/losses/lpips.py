@@ -60,6 +60,9 @@ def validate_state_dict(sd, source: str) -> Dict[str, torch.Tensor]:
     """The tensors this build needs from an LPIPS-alex state dict, checked by name and shape (``ValueError`` naming the key)."""
     if not isinstance(sd, dict):
         raise ValueError(f"--perceptual_weights {source}: expected a torch.save'd dict of tensors, got {type(sd).__name__}")
+    if "net.slice2.3.squeeze.weight" in sd:
+        raise ValueError(f"--perceptual_weights {source}: this is an LPIPS-squeeze file (it holds 'net.slice2.3.squeeze.weight'); it serves --loss=baseline "
+                         "and lpips_kwargs net='squeeze', not the LPIPS-alex losses")
     out = {}
     for key, shape in expected_shapes().items():
         if key not in sd:
@@ -80,8 +83,16 @@ def validate_state_dict(sd, source: str) -> Dict[str, torch.Tensor]:
     return out
 
 
-def load_weights(spec: str) -> Dict[str, torch.Tensor]:
-    """``random:<seed>`` or the path of a ``torch.save``d state dict.  Host only: nothing touches the device."""
+def load_weights(spec: str, net: str = "alex") -> Dict[str, torch.Tensor]:
+    """``random:<seed>`` or the path of a ``torch.save``d state dict in the layout of ``net`` ("alex" | "squeeze", the latter in losses/lpips_squeeze.py).
+    Host only: nothing touches the device."""
+    if net == "squeeze":
+        from . import lpips_squeeze
+        validate, draw = lpips_squeeze.validate_state_dict, lpips_squeeze.random_state_dict
+    elif net == "alex":
+        validate, draw = validate_state_dict, random_state_dict
+    else:
+        raise ValueError(f"--perceptual_weights: no LPIPS network {net!r} in this build (alex, squeeze)")
     if not isinstance(spec, str) or not spec:
         raise ValueError(f"--perceptual_weights must be a file or random:<seed>; got {spec!r}")
     if spec.startswith("random:"):
@@ -89,14 +100,14 @@ def load_weights(spec: str) -> Dict[str, torch.Tensor]:
             seed = int(spec[len("random:"):])
         except ValueError:
             raise ValueError(f"--perceptual_weights {spec!r}: the seed after 'random:' must be an integer") from None
-        return validate_state_dict(random_state_dict(seed), spec)
+        return validate(draw(seed), spec)
     if not os.path.isfile(spec):
         raise ValueError(f"--perceptual_weights {spec!r}: no such file")
     try:
         sd = torch.load(spec, map_location="cpu", weights_only=True)
     except Exception as e:      # noqa: BLE001 -- whatever the unpickler raises, the flag is named
         raise ValueError(f"--perceptual_weights {spec!r}: cannot be read as a torch.save'd state dict ({type(e).__name__}: {e})") from e
-    return validate_state_dict(sd, spec)
+    return validate(sd, spec)
 
 
 def draw_slices(seed: int, step: int, view: int, n_slices: int, n_keep: int) -> np.ndarray:

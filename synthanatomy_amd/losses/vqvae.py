@@ -374,13 +374,29 @@ class WaveGANLoss(_FourierLoss):
         return self.get_fft_factor()
 
 
+def _lpips_network(name: str, net: str, weights: Dict, compute_dtype: torch.dtype):
+    """(the frozen LPIPS network ``net`` over validated weights, its smallest slice side); weights of the other network's layout are refused by name"""
+    from . import lpips, lpips_squeeze
+    squeeze_file = lpips_squeeze.is_squeeze_layout(weights)
+    if net == "squeeze":
+        if not squeeze_file:
+            raise ValueError(f"{name}: net='squeeze' needs perceptual_weights in the layout of lpips.LPIPS(net='squeeze').state_dict() (key "
+                             f"'net.slice2.3.squeeze.weight' is missing): losses.lpips.load_weights(<file> | 'random:<seed>', net='squeeze')")
+        return lpips_squeeze.LpipsSqueeze(weights, compute_dtype), lpips_squeeze.MIN_SIDE
+    if squeeze_file:
+        raise ValueError(f"{name}: perceptual_weights hold the LPIPS-squeeze layout ('net.slice2.3.squeeze.weight'); pass lpips_kwargs={{'net': 'squeeze'}} "
+                         "or LPIPS-alex weights")
+    return lpips.LpipsAlex(weights, compute_dtype), lpips.MIN_SIDE
+
+
 _FAKE_3D_VIEW = {2: 0, 3: 1, 4: 2}      # fake_3d_axis entry -> view id of sa_lpips_unfold (the reference's permutes (0,2,1,3,4), (0,3,1,2,4), (0,4,1,2,3))
 
 
 class _PerceptualLoss(torch.nn.Module):
-    """What ``PerceptualLoss``, ``JukeboxPerceptualLoss`` and ``HartleyPerceptualLoss`` share: the 2.5D LPIPS-alex term (losses/lpips.py, csrc/lpips.hip;
-    DESIGN.md section 7.12), the pixel term and the commitment terms.  Beyond upstream's constructor arguments: ``perceptual_weights`` (a validated
-    LPIPS-alex state dict, losses.lpips.load_weights), ``compute_dtype`` (float32 = parity mode, bfloat16 = throughput mode) and ``seed`` (the slice
+    """What ``PerceptualLoss``, ``JukeboxPerceptualLoss`` and ``HartleyPerceptualLoss`` share: the 2.5D LPIPS term -- alex by default (losses/lpips.py,
+    csrc/lpips.hip), squeeze with ``lpips_kwargs={"net": "squeeze"}`` (losses/lpips_squeeze.py; section 7.13) --, the pixel term and
+    the commitment terms.  Beyond upstream's constructor arguments: ``perceptual_weights`` (a validated state dict in the layout of that network,
+    losses.lpips.load_weights), ``compute_dtype`` (float32 = parity mode, bfloat16 = throughput mode) and ``seed`` (the slice
     draw is keyed on (seed, step, view); the training loop calls :meth:`set_step` with the global iteration)."""
 
     def __init__(self, dimensions: int, include_pixel_loss: bool = True, is_fake_3d: bool = True, drop_ratio: float = 0.0,
@@ -393,11 +409,13 @@ class _PerceptualLoss(torch.nn.Module):
             raise NotImplementedError(f"{name}: only dimensions=3 ([B, 1, D, H, W] volumes, the 2.5D approach) has a HIP path; got dimensions={dimensions}")
         if not is_fake_3d:
             raise NotImplementedError(f"{name}: is_fake_3d=False (a true 3D perceptual loss) is not implemented, as upstream")
+        net = "alex"
         if lpips_kwargs is not None:
             want = {k: v for k, v in lpips.DEFAULT_LPIPS_KWARGS.items() if k != "verbose"}
-            if any(k not in want or want[k] != v for k, v in dict(lpips_kwargs).items() if k != "verbose"):
-                raise NotImplementedError(f"{name}: only the default lpips_kwargs (net='alex', version='0.1', lpips=True, spatial=False, pnet_tune=False) "
-                                          f"have a HIP path; got lpips_kwargs={lpips_kwargs}")
+            net = dict(lpips_kwargs).get("net", "alex")
+            if any(k not in want or (want[k] != v and not (k == "net" and v == "squeeze")) for k, v in dict(lpips_kwargs).items() if k != "verbose"):
+                raise NotImplementedError(f"{name}: only the default lpips_kwargs (net='alex' or 'squeeze', version='0.1', lpips=True, spatial=False, "
+                                          f"pnet_tune=False) have a HIP path; got lpips_kwargs={lpips_kwargs}")
         if isinstance(drop_ratio, bool) or not isinstance(drop_ratio, (int, float)) or not 0 <= drop_ratio < 1:
             raise ValueError(f"{name}: drop_ratio must lie in [0, 1); got drop_ratio={drop_ratio}")
         axes = tuple(fake_3d_axis)
@@ -406,11 +424,11 @@ class _PerceptualLoss(torch.nn.Module):
         if perceptual_weights is None:
             raise ValueError(f"{name}: perceptual_weights is required (this build downloads nothing): losses.lpips.load_weights(<file> | 'random:<seed>')")
         self.dimensions, self.include_pixel_loss = dimensions, include_pixel_loss
-        self.lpips_kwargs = dict(lpips.DEFAULT_LPIPS_KWARGS)
+        self.lpips_kwargs = dict(lpips.DEFAULT_LPIPS_KWARGS, net=net)
         self.fake_3D_views = [_FAKE_3D_VIEW[a] for a in (2, 3, 4) if a in axes]      # (upstream's order: by axis, whatever the tuple's order)
         self.keep_ratio = 1 - drop_ratio
         self.lpips_normalize = bool(lpips_normalize)
-        self.perceptual_function = lpips.LpipsAlex(perceptual_weights, compute_dtype)
+        self.perceptual_function, self._min_side = _lpips_network(name, net, perceptual_weights, compute_dtype)
         self.perceptual_factor = 0.001
         self.seed, self.step = int(seed), 0
         self.chunk_slices = None           # None: from the workspace cap (tests halve it)
@@ -425,7 +443,6 @@ class _PerceptualLoss(torch.nn.Module):
         return int(n_slices * self.keep_ratio)
 
     def _check(self, y_pred: torch.Tensor, y: torch.Tensor):
-        from . import lpips
         name = type(self).__name__
         if y_pred.dim() != 5:
             raise ValueError(f"{name} needs [B, 1, D, H, W] volumes; got {tuple(y_pred.shape)}")
@@ -436,9 +453,9 @@ class _PerceptualLoss(torch.nn.Module):
         B, _, D, H, W = y_pred.shape
         for v in self.fake_3D_views:
             n, sides = ((D, (H, W)), (H, (D, W)), (W, (D, H)))[v]
-            if min(sides) < lpips.MIN_SIDE:
-                raise ValueError(f"{name}: view {v} has slices of {sides[0]} x {sides[1]}; every slice side must be >= {lpips.MIN_SIDE} (the smallest for which "
-                                 f"AlexNet's second pool still has an output); got a volume of {D} x {H} x {W}")
+            if min(sides) < self._min_side:
+                raise ValueError(f"{name}: view {v} has slices of {sides[0]} x {sides[1]}; every slice side must be >= {self._min_side} (the smallest for which "
+                                 f"the network's last pool still has an output); got a volume of {D} x {H} x {W}")
             if self._n_keep(B * n) < 1:
                 raise ValueError(f"{name}: drop_ratio={1 - self.keep_ratio:g} keeps 0 of the {B * n} slices of view {v}")
 
@@ -551,8 +568,130 @@ class HartleyPerceptualLoss(_PerceptualLoss):
         return self._hartley.set_fht_factor(fht_factor)
 
 
-# of the reference's src/losses/vqvae/utils.py list; the LPIPS family needs --perceptual_weights (this build downloads nothing); "baseline" (SqueezeNet) is out of scope
-VQVAE_LOSSES = ("baur", "mse", "jukebox", "spectral", "hartley", "wavegan", "perceptual", "jukebox_perceptual", "hartley_perceptual")
+class _BaselinePerceptualFn(torch.autograd.Function):
+    """``perceptual_factor * (mean LPIPS over the kept sagittal slices + axial + coronal)`` and its gradient to the prediction, computed in the forward pass;
+    returns the differentiable scaled sum and the three UNSCALED per-view means (sagittal, axial, coronal) as non-differentiable side outputs."""
+
+    VIEWS = (0, 2, 1)       # sagittal (0,2,1,3,4), axial (0,4,1,2,3), coronal (0,3,1,2,4): upstream's order of evaluation and of the sum
+
+    @staticmethod
+    def forward(ctx, pred, target, net, ids, factor: float, chunk):
+        _ffi.require_gpu()
+        a = pred.contiguous()
+        b = target.contiguous().to(a.device)
+        grad = torch.zeros_like(a) if pred.requires_grad else None
+        means = []
+        for view, vid in zip(_BaselinePerceptualFn.VIEWS, ids):
+            d = net.view_term(b, a, view, vid, grad, factor / vid.numel(), False, chunk)     # (upstream calls LPIPS without normalize)
+            means.append(d.double().sum().div(vid.numel()).float())
+        total = ((means[0] + means[1]) + means[2]) * factor
+        ctx.grad = grad
+        ctx.mark_non_differentiable(*means)
+        return (total, *means)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        # re-entrant like _MSEFn: the stored d loss / d pred is neither consumed nor scaled in place
+        grad = ctx.grad
+        return (grad * g if grad is not None else None), None, None, None, None, None
+
+
+class BaselineLoss(torch.nn.Module):
+    """``BaselineLoss()`` of the reference (src/losses/vqvae/vqvae.py:1648-1780, ``--loss=baseline``): ``pixel_factor * l1(pred, y) + fft_factor *
+    mse(|fftn((y + 1) / 2)|, |fftn((pred + 1) / 2)|) + perceptual_factor * (three-plane mean LPIPS-squeeze) + sum(quantization_losses)``.
+
+    * perceptual term: losses/lpips_squeeze.py: per plane ``min(n_slices, B n)`` slices, drawn by ``lpips.draw_slices(seed, step,
+      view, ...)`` -- the project's draw, standing in for upstream's ``torch.randperm`` --, LPIPS WITHOUT ``normalize`` (upstream passes the volumes as they are);
+    * frequency term: upstream's ``fftn`` names no ``dim``, so it transforms ALL five axes, the batch included.  With C = 1 that is :class:`JukeboxLoss`'
+      amplitude term on the volumes viewed as [1, B, D, H, W] (the batch takes the channel axis' place): rocFFT through ``torch.fft.fftn``, with
+      upstream's ``torch.abs`` (zero gradient at an empty bin, so constant volumes stay finite);
+    * pixel term: ``F.l1_loss``, a bandwidth-trivial pass of torch's elementwise operators (``sa_baur_loss`` cannot leave its L2 term out).
+
+    Upstream's constructor takes no arguments; this build adds ``perceptual_weights`` (a validated LPIPS-squeeze state dict), ``compute_dtype`` and ``seed``.
+    ``pixel_factor``, ``perceptual_factor``, ``n_slices`` and ``fft_factor`` are plain settable attributes and the summary keys are upstream's."""
+
+    def __init__(self, *, perceptual_weights: Dict = None, compute_dtype: torch.dtype = torch.float32, seed: int = 0):
+        super().__init__()
+        if perceptual_weights is None:
+            raise ValueError("BaselineLoss: perceptual_weights is required (this build downloads nothing): "
+                             "losses.lpips.load_weights(<file> | 'random:<seed>', net='squeeze')")
+        self.pixel_factor = 1.0
+        self.perceptual_factor = 0.002
+        self.n_slices = 512
+        self.perceptual_function, self._min_side = _lpips_network("BaselineLoss", "squeeze", perceptual_weights, compute_dtype)
+        self.fft_factor = 1.0
+        self.seed, self.step = int(seed), 0
+        self.chunk_slices = None           # None: from the workspace cap (tests set it)
+        self.summaries: Dict = {"scalar": {}}
+
+    def set_step(self, step: int) -> int:
+        """the global training iteration: with the seed and the view it keys the slice draw, so a resumed run reproduces it"""
+        self.step = int(step)
+        return self.step
+
+    def _check(self, y_pred: torch.Tensor, y: torch.Tensor):
+        if y_pred.dim() != 5:
+            raise ValueError(f"BaselineLoss needs [B, 1, D, H, W] volumes; got {tuple(y_pred.shape)}")
+        if tuple(y.shape) != tuple(y_pred.shape):
+            raise ValueError(f"BaselineLoss: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
+        if y_pred.shape[1] != 1:
+            raise NotImplementedError(f"BaselineLoss: C = 1 only (the single channel broadcasts to LPIPS' three); got C={y_pred.shape[1]}")
+        if min(y_pred.shape[2:]) < self._min_side:
+            raise ValueError(f"BaselineLoss: every slice side must be >= {self._min_side} (the smallest for which SqueezeNet's third ceil-mode pool still has "
+                             f"an output); got a volume of {' x '.join(map(str, y_pred.shape[2:]))}")
+        if int(self.n_slices) < 1:
+            raise ValueError(f"BaselineLoss: n_slices must be >= 1; got {self.n_slices}")
+
+    def _calculate_pixel_loss(self, y_pred, y):
+        loss = torch.nn.functional.l1_loss(y_pred, y) * self.pixel_factor
+        self.summaries["scalar"]["Loss-MAE-Reconstruction"] = loss.detach()
+        return loss
+
+    def _calculate_frequency_loss(self, y_pred, y):
+        shape = (1, *y_pred.shape[:1], *y_pred.shape[2:])
+
+        def amplitude(t):
+            # the affine (t + 1) / 2 is one elementwise pass in front of the transform; torch.abs, as upstream: its gradient at an empty bin is 0, not NaN
+            return torch.abs(torch.fft.fftn(((t + 1.0) * 0.5).reshape(shape), dim=_FFT_DIMS, norm="ortho"))
+
+        with torch.no_grad():
+            y_amp = amplitude(y)
+        loss = torch.nn.functional.mse_loss(amplitude(y_pred), y_amp) * self.fft_factor
+        self.summaries["scalar"]["Loss-Jukebox-Reconstruction"] = loss.detach()
+        return loss
+
+    def _calculate_perceptual_loss(self, y_pred, y):
+        from . import lpips
+        B, _, D, H, W = y_pred.shape
+        ids = []
+        for v in _BaselinePerceptualFn.VIEWS:         # small int32 uploads; every refusal comes before the first launch
+            n = B * (D, H, W)[v]
+            ids.append(torch.from_numpy(lpips.draw_slices(self.seed, self.step, v, n, min(int(self.n_slices), n))).to(y_pred.device))
+        loss, sag, axi, cor = _BaselinePerceptualFn.apply(y_pred, y, self.perceptual_function, ids, float(self.perceptual_factor), self.chunk_slices)
+        self.summaries["scalar"]["Loss-Perceptual_Sagittal-Reconstruction"] = sag.detach()
+        self.summaries["scalar"]["Loss-Perceptual_Axial-Reconstruction"] = axi.detach()
+        self.summaries["scalar"]["Loss-Perceptual_Coronal-Reconstruction"] = cor.detach()
+        self.summaries["scalar"]["Loss-Perceptual-Reconstruction"] = loss.detach()
+        return loss
+
+    def forward(self, network_output: Dict[str, List[torch.Tensor]], y: torch.Tensor) -> torch.Tensor:
+        y = y.float()
+        y_pred = network_output["reconstruction"][0].float()
+        self._check(y_pred, y)
+        y = y.to(y_pred.device)
+        loss = self._calculate_pixel_loss(y_pred, y) + self._calculate_frequency_loss(y_pred, y) + self._calculate_perceptual_loss(y_pred, y)
+        for idx, ql in enumerate(network_output["quantization_losses"]):
+            ql = ql.float()
+            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
+            loss = loss + ql
+        return loss
+
+    def get_summaries(self):
+        return self.summaries
+
+
+# the reference's src/losses/vqvae/utils.py list, complete; the LPIPS family and "baseline" (LPIPS-squeeze) need --perceptual_weights (this build downloads nothing)
+VQVAE_LOSSES = ("baur", "mse", "jukebox", "spectral", "hartley", "wavegan", "perceptual", "jukebox_perceptual", "hartley_perceptual", "baseline")
 _PERCEPTUAL_LOSSES = {"perceptual": PerceptualLoss, "jukebox_perceptual": JukeboxPerceptualLoss, "hartley_perceptual": HartleyPerceptualLoss}
 
 
@@ -579,5 +718,13 @@ def get_vqvae_loss(config: dict) -> torch.nn.Module:
         dtype = config.get("compute_dtype") or (torch.bfloat16 if config.get("amp") else torch.float32)
         return _PERCEPTUAL_LOSSES[config["loss"]](dimensions=3, drop_ratio=0.5, perceptual_weights=weights, compute_dtype=dtype,
                                                   seed=int(config.get("seed") or 0))
-    hint = " The LPIPS family needs --perceptual_weights=<file | random:seed>." if config["loss"] in _PERCEPTUAL_LOSSES else ""
+    if config["loss"] == "baseline" and config.get("perceptual_weights"):
+        # src/losses/vqvae/configure.py builds BaselineLoss() without arguments; the LPIPS-squeeze weights come from --perceptual_weights
+        from . import lpips
+        weights = config["perceptual_weights"]
+        if not isinstance(weights, dict):
+            weights = lpips.load_weights(weights, net="squeeze")
+        dtype = config.get("compute_dtype") or (torch.bfloat16 if config.get("amp") else torch.float32)
+        return BaselineLoss(perceptual_weights=weights, compute_dtype=dtype, seed=int(config.get("seed") or 0))
+    hint = " The LPIPS family needs --perceptual_weights=<file | random:seed>." if config["loss"] in (*_PERCEPTUAL_LOSSES, "baseline") else ""
     raise ValueError(f"Loss function unknown. Was given {config['loss']} but choices are {list(VQVAE_LOSSES)}.{hint}")
