@@ -188,6 +188,21 @@ int sa_vq_assign(const float *rows, const float *codebook, int64_t M, int K, int
 /* baseline.py:75-80: N <- g N + (1-g) counts; embed_avg <- g embed_avg + (1-g) dw; codebook <- embed_avg / smoothed N */
 int sa_vq_ema_update(float *N, float *embed_avg, float *codebook, const float *counts, const float *dw, int K, int D,
                      float decay, float eps, void *stream);
+/* Dead-code restarts: an opt-in extension of the EMA update above (the call site baseline.py:66-80; the rule is this project's own).
+ * sa_vq_restart_donors: donors[R, D] <- R rows of this step's encoder output, drawn without looking at the codes.  Mtot = rows of all ranks (this rank holds the
+ * global rows row_base .. row_base + M - 1), R_eff = min(R, Mtot), stride = Mtot / R_eff, slot j < R_eff takes global row g_j = j stride + (w_j mod stride) with
+ * w_j = word 0 of philox4x32_10(counter (j, lo32 step, hi32 step, 0x56515253), key (lo32 seed, hi32 seed)).  EVERY slot is written on every call: the row when this
+ * rank holds it, zeros otherwise (and for j >= R_eff), so the sum of all ranks' buffers (the caller's all-reduce) is the donor matrix exactly.
+ * SA_EINVAL: null pointer, M <= 0, D <= 0, R outside 1..64, row_base < 0, Mtot < row_base + M.  SA_EUNSUPPORTED: D not a multiple of 8.
+ * sa_vq_ema_update_restart: idle[k] <- counts[k] > 0 ? 0 : min(idle[k] + 1, INT32_MAX) (counts = the all-reduced statistics); a code is dead when idle[k] >= patience;
+ * the first min(dead, R) dead codes in ascending k are restarted, the i-th of them from donors[i] (R = the number of valid donor rows, the gather's R_eff): the
+ * launch is then bit for bit sa_vq_ema_update on inputs in which every restarted code has N = 0, embed_avg = 0, counts = 1, dw = its donor row, and its idle
+ * counter returns to 0; the other dead codes keep counting.  info (int32 [2 + R]): dead codes found, codes restarted, their ids ascending, padded with -1.
+ * SA_EINVAL: null pointer, K <= 0, D <= 0, R outside 1..64, patience < 1.  SA_EUNSUPPORTED: D not a multiple of 8. */
+int sa_vq_restart_donors(const float *rows, int64_t M, int D, int64_t row_base, int64_t Mtot, int R, uint64_t seed, uint64_t step, float *donors,
+                         void *stream);
+int sa_vq_ema_update_restart(float *N, float *embed_avg, float *codebook, const float *counts, const float *dw, int K, int D, float decay, float eps,
+                             int32_t *idle, int patience, const float *donors, int R, int32_t *info, void *stream);
 /* baseline.py:110-120: perplexity = exp(-sum p log(p+1e-10)), p = counts / M */
 int sa_vq_perplexity(const float *counts, int K, int64_t M, float *out, void *stream);
 /* gradient of (zq_st, loss) wrt the encoder output: dz = g_zq + g_loss * beta * 2 (x - W[idx]) / (M D)   (baseline.py:82-85) */

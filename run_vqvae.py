@@ -36,6 +36,13 @@ auto-scaled to the full code range (scl_slope / scl_inter in the header).  ``--n
 is decoded.  The code files stay uint16 ``.npy``.  The flags act or refuse: an unknown value, an integer dtype with ``.npy``, a NIfTI extension with
 ``--mode=training`` or with ``--no_augmented_extractions > 0`` raise a ``ValueError`` before anything runs.
 
+``--codebook_restart_patience=<steps>`` (MI355X-only; default None: nothing changes) restarts dead codes of the EMA codebook: a code that no
+encoder output of any rank chose for that many consecutive training steps is re-seeded from a row of the current step's encoder output, at most
+``--codebook_restart_max`` (default 32, 1..64) codes per step, inside the EMA update's launch (``sa_vq_ema_update_restart``).  The draw is keyed on
+(``--seed``, global iteration), the counters travel in the checkpoint's ``codebook_restart`` entry, and the log line gains ``codebook_dead <n> restarted <r>``.
+``--decay_warmup=step|linear`` with ``--max_decay_epochs=<n>|auto`` schedules the EMA decay from ``--decay`` to 0.99 at every finished epoch
+(networks/vqvae/configure.py: decay_schedule).  All four flags act or refuse by name before anything touches the device.
+
 ``--mode=anomaly`` (MI355X-only; the rule is this project's own) is the last stage of the healing application: every ``--validation_subjects``
 scan goes through the usual input path, the files ``run_transformer.py --mode=healing`` wrote for its codes (``<stem>_quantization_0_healed_sample.npy``,
 ``..._resampled.npy``, ``..._nll.npy``) are found by stem under ``--anomaly_codes=<dir|glob>`` (default: this experiment's outputs directory), the healed
@@ -71,6 +78,7 @@ DEFAULTS = dict(
     num_embeddings=(256,), embedding_dim=(256,), embedding_init=("normal",), commitment_cost=(0.25,), decay=(0.99,), decay_warmup=None,
     max_decay_epochs=50, norm=None, dropout=0.0, act="RELU", output_act=None, evaluation_checkpoint="recent", load_nii_canonical=True,
     output_ext=".npy", output_dtype="float32", perceptual_weights=None,
+    codebook_restart_patience=None, codebook_restart_max=32,
     anomaly_codes=None, anomaly_weight="mask", anomaly_sigma=None, anomaly_residual="abs", anomaly_threshold=None, anomaly_hist_max=1.0, anomaly_labels=None,
 )
 MODES = ["training", "extracting", "decoding", "anomaly"]
@@ -90,6 +98,27 @@ def _check_output_flags(cfg):
     if ext != ".npy" and n_aug > 0:
         raise ValueError(f"--output_ext={ext} with --no_augmented_extractions={n_aug}: augmented extractions are not on the source grid and exist for "
                          "their codes; leave --output_ext at .npy")
+
+
+def _check_codebook_flags(cfg):
+    """--codebook_restart_patience / --codebook_restart_max and --decay_warmup / --max_decay_epochs act or refuse, before anything touches the
+    device."""
+    from synthanatomy_amd.networks.vqvae.baseline import check_restart_args
+    from synthanatomy_amd.networks.vqvae.configure import check_decay_warmup
+    check_decay_warmup(cfg)
+    p, r = cfg["codebook_restart_patience"], cfg["codebook_restart_max"]
+    if p is not None and cfg["mode"] != "training":
+        raise ValueError(f"--codebook_restart_patience={p}: codes are restarted by training steps (--mode=training), not by --mode={cfg['mode']}")
+    if r != DEFAULTS["codebook_restart_max"] and cfg["mode"] != "training":
+        raise ValueError(f"--codebook_restart_max={r}: codes are restarted by training steps (--mode=training), not by --mode={cfg['mode']}")
+    try:
+        check_restart_args(1 if p is None else p, r)
+    except ValueError as e:
+        raise ValueError(f"--{e}") from None
+    if p is None and r != DEFAULTS["codebook_restart_max"]:
+        raise ValueError(f"--codebook_restart_max={r} needs --codebook_restart_patience=<steps>: without it no code is ever restarted")
+    if p is not None and cfg["codebook_type"] != "ema":
+        raise ValueError(f"--codebook_restart_patience={p}: restarts belong to the EMA quantizer (--codebook_type=ema)")
 
 
 def _check_perceptual_flags(cfg):
@@ -290,6 +319,7 @@ def training(cfg, rank, local, world, dev):
     from synthanatomy_amd.engines.trainer import AdversarialTrainer
     from synthanatomy_amd.losses.adversarial import get_discriminator_loss, get_generator_loss
     from synthanatomy_amd.losses.vqvae import gdl_factor_schedule, get_vqvae_loss
+    from synthanatomy_amd.networks.vqvae.configure import decay_schedule
     from synthanatomy_amd.runtime.ddp import GradReducer
     from synthanatomy_amd.runtime.optim import ExponentialLR, FlatParams, FusedAdam, TrainerState
     loss_fn = get_vqvae_loss(dict(cfg, perceptual_weights=cfg.get("perceptual_state") or cfg.get("perceptual_weights")))
@@ -320,6 +350,12 @@ def training(cfg, rank, local, world, dev):
     epoch_length = cfg["training_epoch_length"] or (per_rank + cfg["batch_size"] - 1) // cfg["batch_size"]
     state = TrainerState(epoch_length=epoch_length, max_epochs=cfg["epochs"])
     to_save = {"network": net, "optimizer": opt, "lr_scheduler": sched, "trainer": state}
+    restarting = cfg["codebook_restart_patience"] is not None      # dead-code restarts: the donor draw is keyed on (--seed, global iteration)
+    if restarting:
+        net.set_codebook_restart(cfg["codebook_restart_patience"], cfg["codebook_restart_max"], cfg["seed"])
+        to_save["codebook_restart"] = net.codebook_restart_state()      # idle counters + running total: resuming equals not stopping
+    warming = cfg["decay_warmup"] is not None                      # EMA decay scheduled at every finished epoch (networks/vqvae/configure.py: decay_schedule)
+    decay_cfg = dict(cfg, epoch_length=epoch_length)
     trainer = None
     if cfg["adversarial_component"]:
         from synthanatomy_amd.networks.discriminator.configure import get_discriminator_network
@@ -338,13 +374,20 @@ def training(cfg, rank, local, world, dev):
     # resume (run_vqvae.py:328-345): everything in to_save, except the d_* entries when the adversarial component is being fine-tuned in
     ckpt = check_for_checkpoints(cfg)
     if ckpt:
-        to_load = {k: v for k, v in to_save.items() if not (cfg["finetune_adversarial_component"] and k.startswith("d_"))}
-        load_checkpoint(ckpt, to_load, map_location=dev)
+        to_load = {k: v for k, v in to_save.items() if not (cfg["finetune_adversarial_component"] and k.startswith("d_")) and k != "codebook_restart"}
+        loaded = load_checkpoint(ckpt, to_load, map_location=dev)
+        if restarting and "codebook_restart" in loaded:
+            to_save["codebook_restart"].load_state_dict(loaded["codebook_restart"])
+        elif restarting:
+            log(rank, f"{ckpt} has no codebook_restart entry (written without --codebook_restart_patience): the idle counters start at zero")
         state.rebase(epoch_length, cfg["epochs"])      # finished epochs by the CHECKPOINT's epoch length; this run's data set / --epochs decide the rest
         net.invalidate_packed_weights()
         log(rank, f"resumed from {ckpt}: epoch {state.epoch}, iteration {state.iteration}, lr {opt.lr:.6e}")
         if baur and state.epoch > 0:      # (upstream restarts at the class default 0.0 for this epoch; resuming equals not stopping here)
             loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, state.epoch))
+        if warming:
+            net.set_ema_decay(decay_schedule(decay_cfg, state.epoch))
+            log(rank, f"resumed with --decay_warmup={cfg['decay_warmup']}: decay {net.get_ema_decay()[0]:.6g}")
     # key metric (run_vqvae.py:122): MS-SSIM with get_ms_ssim_window's window; where the reference refuses to start (smallest side < 48), -MSE
     from synthanatomy_amd.utils.vqvae import get_ms_ssim_window
     try:      # (--augmentation with --patch_size: the evaluator sees patches, so they size the window unless --eval_patch_size does)
@@ -369,6 +412,8 @@ def training(cfg, rank, local, world, dev):
         for names, x, *noise_seed in batches:
             if perceptual:
                 loss_fn.set_step(state.iteration * world + rank)
+            if restarting:
+                net.set_codebook_restart_step(state.iteration)      # identical on all ranks
             if trainer is not None:
                 res = trainer.iteration(x, x, epoch + 1)      # ignite's state.epoch is 1 during the first epoch (trainer.py:176)
                 loss = res["loss"]
@@ -390,12 +435,18 @@ def training(cfg, rank, local, world, dev):
                     extra += "".join(f" {k} {float(v):.6g}" for k, v in loss_fn.get_summaries()["scalar"].items() if k.startswith("Loss-" if cfg["loss"] == "baseline" else "Loss-Perceptual_"))
                 if augmenting:
                     extra += f" input {'x'.join(str(n) for n in x.shape[2:])} noise_seed {noise_seed[0]:#018x}"
+                if restarting:
+                    info = net.get_codebook_restart_info()
+                    extra += f" codebook_dead {info['dead']} restarted {info['restarted']}"
                 log(rank, f"epoch {epoch} it {state.iteration} loss {loss.item():.6f}{extra} perplexity {net.get_perplexity()[0].item():.2f} lr {opt.lr:.3e}")
             if done == epoch_length:
                 break
         state.iteration = (epoch + 1) * epoch_length      # (a short last batch list still closes the epoch)
         if baur:                                          # ParamSchedulerHandler(epoch_level=True) at EPOCH_COMPLETED, state.epoch = finished epochs
             loss_fn.set_gdl_factor(gdl_factor_schedule(cfg, epoch + 1))
+        if warming:                                       # the same handler on set_ema_decay (src/networks/vqvae/configure.py:42-86)
+            net.set_ema_decay(decay_schedule(decay_cfg, epoch + 1))
+            log(rank, f"epoch {epoch} decay {net.get_ema_decay()[0]:.6g}")
         if (epoch + 1) % cfg["eval_every"] == 0 and val_files:
             mse, metrics = _evaluate(net, val_files, cfg, gen, dev, rank, world, win_size, epoch=epoch, index_base=len(files))
             log(rank, f"epoch {epoch} validation mse {mse:.6f}")
@@ -633,6 +684,7 @@ def run(argv):
     if cfg["mode"] not in MODES:
         raise ValueError(f"VQVAE mode unknown. Was given {cfg['mode']} but choices are {MODES}.")
     _check_output_flags(cfg)
+    _check_codebook_flags(cfg)
     if cfg["mode"] == "anomaly":
         _check_anomaly_flags(cfg)
     cfg["perceptual_state"] = _check_perceptual_flags(cfg) if cfg["mode"] == "training" else None

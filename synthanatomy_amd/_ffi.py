@@ -115,7 +115,10 @@ _SIGS = {
     "sa_colsum": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "sa_vq_assign": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sa_vq_ema_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
-    "sa_vq_perplexity": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "sa_vq_restart_donors": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int, ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p]),
+    "sa_vq_ema_update_restart": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_int,
+                                         c_void_p, c_void_p]),
+    "sa_vq_perplexity": (c_int,[c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "sa_vq_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_int64, c_int, c_void_p, c_int, c_void_p]),
     "sa_vq_embed": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
     "sa_cast_pad": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int64, c_void_p]),

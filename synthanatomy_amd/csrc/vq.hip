@@ -8,6 +8,7 @@
 // emits zq_st = (W[idx]-x)+x, the commitment error, and scatter-adds the EMA sufficient statistics
 // counts[K], dw[K,D] (fp32 atomics; summed over ranks by one RCCL all-reduce on the host side).
 #include "sa_common.h"
+#include "dropout.h"
 
 namespace sa {
 
@@ -236,6 +237,149 @@ __global__ __launch_bounds__(1024) void vq_ema_kernel(float* __restrict__ N, flo
     }
 }
 
+// ---- dead-code restarts (this project's rule, not the reference's) ---------------------------------------------------------------------
+// four consecutive floats: one 16-byte access when the caller's buffers are 16-byte aligned (VEC), four dword accesses otherwise (a packed
+// [counts | dw | donors] buffer whose K is no multiple of 4)
+template <bool VEC> __device__ __forceinline__ float4 vq_ld4(const float* p) {
+    if (VEC) return *(const float4*)p;
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+template <bool VEC> __device__ __forceinline__ void vq_st4(float* p, const float4& v) {
+    if (VEC) {
+        *(float4*)p = v;
+        return;
+    }
+    p[0] = v.x;
+    p[1] = v.y;
+    p[2] = v.z;
+    p[3] = v.w;
+}
+
+// Donor rows: slot j < R_eff = min(R, Mtot) holds global row g_j = j * stride + (w_j mod stride), stride = Mtot / R_eff, w_j = word 0 of
+// philox4x32_10((j, lo32(step), hi32(step), 0x56515253), (lo32(seed), hi32(seed))): one row per stratum, drawn without looking at the codes.  One block per slot;
+// a block whose row lives on another rank (outside [row_base, row_base + M)) and the slots beyond R_eff write zeros, so the SUM of all ranks' buffers is the
+// donor matrix exactly (x + 0 is exact).
+template <bool VEC>
+__global__ __launch_bounds__(64) void vq_restart_donors_kernel(const float* __restrict__ rows, int64_t M, int D, int64_t row_base, int64_t Mtot, int R_eff,
+                                                               uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1, float* __restrict__ donors) {
+    const int j = blockIdx.x;
+    int64_t local = -1;
+    if (j < R_eff) {
+        const uint64_t stride = (uint64_t)(Mtot / R_eff);
+        const uint32_t w = philox4x32_10((uint32_t)j, s0, s1, 0x56515253u, k0, k1).v[0];
+        const int64_t g = (int64_t)((uint64_t)j * stride + (uint64_t)w % stride);
+        if (g >= row_base && g < row_base + M) local = g - row_base;
+    }
+    float* dst = donors + (int64_t)j * D;
+    const float* src = local >= 0 ? rows + local * D : nullptr;
+    for (int c = threadIdx.x * 4; c < D; c += 256) vq_st4<VEC>(dst + c, src ? vq_ld4<VEC>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
+// sa_vq_ema_update with the restart rule in front, one launch in vq_ema_kernel's shape.  Codes go through the block in ascending chunks of 1024 (thread tid owns
+// k = tid, tid + 1024, ..., exactly the k loop of vq_ema_kernel, so the per-thread order of the ntot sum is the same): idle update, dead flag, the rank of every
+// dead code among the dead ones in ascending k (ballot + popcount inside a wave, the 16 wave totals through LDS, the chunk total carried in a register that every
+// thread computes alike), and for rank < R the EMA line on the SUBSTITUTED inputs N_old = 0, counts = 1 -- literally, so the launch is bit for bit vq_ema_kernel
+// on inputs in which every restarted code has N_old = 0, embed_avg_old = 0, counts = 1, dw = its donor row.  sid[rank] = k (ascending) is what the element loop
+// searches to find a code's donor slot.
+template <bool VEC>
+__global__ __launch_bounds__(1024) void vq_ema_restart_kernel(float* __restrict__ N, float* __restrict__ avg, float* __restrict__ cb,
+                                                              const float* __restrict__ counts, const float* __restrict__ dw, int K, int D, float decay,
+                                                              float eps, int* __restrict__ idle, int patience, const float* __restrict__ donors, int R,
+                                                              int* __restrict__ info) {
+    __shared__ float red[16];
+    __shared__ float ntot;
+    __shared__ int wcnt[16];
+    __shared__ int sid[64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float omd = 1.f - decay;
+    float s = 0.f;
+    int base = 0;      // dead codes in the chunks before this one (the same value on every thread)
+    for (int k0 = 0; k0 < K; k0 += 1024) {
+        const int k = k0 + tid;
+        bool dead = false;
+        int idl = 0;
+        float cnt = 0.f;
+        if (k < K) {
+            cnt = counts[k];
+            const int old = idle[k];
+            idl = cnt > 0.f ? 0 : (old < 0x7fffffff ? old + 1 : 0x7fffffff);
+            dead = idl >= patience;
+        }
+        const unsigned long long m = __ballot(dead);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int c = wcnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        __syncthreads();      // (wcnt is rewritten by the next chunk)
+        if (k < K) {
+            const int rank = base + before + __popcll(m & ((1ull << lane) - 1ull));
+            const bool restart = dead && rank < R;
+            float nold = N[k];
+            if (restart) {
+                sid[rank] = k;
+                nold = 0.f;
+                cnt = 1.f;
+                idl = 0;
+            }
+            const float v = __fadd_rn(__fmul_rn(nold, decay), __fmul_rn(cnt, omd));
+            N[k] = v;
+            idle[k] = idl;
+            s += v;
+        }
+        base += total;
+    }
+    const int nres = base < R ? base : R;
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();      // (also: N[] and sid[] of every thread are visible from here on)
+    if (tid == 0) {
+        float t = 0.f;
+        for (int i = 0; i < 16; ++i) t += red[i];
+        ntot = t;
+    }
+    if (tid < R + 2) info[tid] = tid == 0 ? base : tid == 1 ? nres : (tid - 2 < nres ? sid[tid - 2] : -1);
+    __syncthreads();
+    const float n = ntot;
+    const float denom = __fadd_rn(n, __fmul_rn((float)K, eps));
+    const int D4 = D >> 2;
+    const int64_t n4 = (int64_t)K * D4;
+    const int lo = nres > 0 ? sid[0] : 0, hi = nres > 0 ? sid[nres - 1] : -1;
+    for (int64_t e4 = tid; e4 < n4; e4 += 1024) {
+        const int k = (int)(e4 / D4);
+        const int c4 = (int)(e4 - (int64_t)k * D4);
+        int slot = -1;
+        if (k >= lo && k <= hi) {      // binary search of k in sid[0 .. nres) (ascending)
+            int a = 0, b = nres - 1;
+            while (a < b) {
+                const int mid = (a + b) >> 1;
+                if (sid[mid] < k) a = mid + 1;
+                else b = mid;
+            }
+            if (sid[a] == k) slot = a;
+        }
+        const float wn = __fmul_rn(__fdiv_rn(__fadd_rn(N[k], eps), denom), n);
+        float4 ao = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 d;
+        if (slot >= 0) d = vq_ld4<VEC>(donors + (int64_t)slot * D + c4 * 4);
+        else {
+            ao = vq_ld4<VEC>(avg + e4 * 4);
+            d = vq_ld4<VEC>(dw + e4 * 4);
+        }
+        float4 a;
+        a.x = __fadd_rn(__fmul_rn(ao.x, decay), __fmul_rn(d.x, omd));
+        a.y = __fadd_rn(__fmul_rn(ao.y, decay), __fmul_rn(d.y, omd));
+        a.z = __fadd_rn(__fmul_rn(ao.z, decay), __fmul_rn(d.z, omd));
+        a.w = __fadd_rn(__fmul_rn(ao.w, decay), __fmul_rn(d.w, omd));
+        vq_st4<VEC>(avg + e4 * 4, a);
+        vq_st4<VEC>(cb + e4 * 4, make_float4(__fdiv_rn(a.x, wn), __fdiv_rn(a.y, wn), __fdiv_rn(a.z, wn), __fdiv_rn(a.w, wn)));
+    }
+}
+
 __global__ __launch_bounds__(1024) void vq_perplexity_kernel(const float* __restrict__ counts, int K, float inv_m, float* __restrict__ out) {
     __shared__ float red[16];
     float s = 0.f;
@@ -306,6 +450,37 @@ extern "C" int sa_vq_ema_update(float* N, float* embed_avg, float* codebook, con
     using namespace sa;
     if (!N || !embed_avg || !codebook || !counts || !dw || K <= 0 || D <= 0) return SA_EINVAL;
     SA_LAUNCH(vq_ema_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, N, embed_avg, codebook, counts, dw, K, D, decay, eps);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sa_vq_restart_donors(const float* rows, int64_t M, int D, int64_t row_base, int64_t Mtot, int R, uint64_t seed, uint64_t step,
+                                    float* donors, void* stream) {
+    using namespace sa;
+    if (!rows || !donors || M <= 0 || D <= 0 || R < 1 || R > 64 || row_base < 0 || Mtot < row_base + M) return SA_EINVAL;
+    if (D & 7) return SA_EUNSUPPORTED;
+    const int R_eff = Mtot < (int64_t)R ? (int)Mtot : R;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
+    if ((((uintptr_t)rows | (uintptr_t)donors) & 15) == 0)
+        SA_LAUNCH(vq_restart_donors_kernel<true>, dim3(R), dim3(64), 0, (hipStream_t)stream, rows, M, D, row_base, Mtot, R_eff, k0, k1, s0, s1, donors);
+    else
+        SA_LAUNCH(vq_restart_donors_kernel<false>, dim3(R), dim3(64), 0, (hipStream_t)stream, rows, M, D, row_base, Mtot, R_eff, k0, k1, s0, s1, donors);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sa_vq_ema_update_restart(float* N, float* embed_avg, float* codebook, const float* counts, const float* dw, int K, int D, float decay,
+                                        float eps, int32_t* idle, int patience, const float* donors, int R, int32_t* info, void* stream) {
+    using namespace sa;
+    if (!N || !embed_avg || !codebook || !counts || !dw || !idle || !donors || !info || K <= 0 || D <= 0) return SA_EINVAL;
+    if (R < 1 || R > 64 || patience < 1) return SA_EINVAL;
+    if (D & 7) return SA_EUNSUPPORTED;
+    if ((((uintptr_t)embed_avg | (uintptr_t)codebook | (uintptr_t)dw | (uintptr_t)donors) & 15) == 0)
+        SA_LAUNCH(vq_ema_restart_kernel<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, N, embed_avg, codebook, counts, dw, K, D, decay, eps, idle, patience,
+                  donors, R, info);
+    else
+        SA_LAUNCH(vq_ema_restart_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, N, embed_avg, codebook, counts, dw, K, D, decay, eps, idle, patience,
+                  donors, R, info);
     SA_CHECK_LAUNCH();
     return 0;
 }

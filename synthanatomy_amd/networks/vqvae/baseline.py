@@ -43,14 +43,50 @@ class Quantizer_impl(nn.Module):
         self._side = None
         self._ema_done = None
         self.process_group = None
+        # dead-code restarts (off by default: nothing below exists then and the step is the two launches above)
+        self._restart = None          # (patience, max_per_step, seed)
+        self._restart_step = 0        # the global iteration of the NEXT training forward: counter of the donor draw
+        self._restart_info = None     # int32 [2 + max_per_step] on the device: dead, restarted, ids of the last training step
 
     # ---- device buffers -------------------------------------------------------------------------------------
     def _work_buffers(self, dev):
         K, D = self.n_embed, self.embed_dim
-        if self._stats is None or self._stats.device != dev:
-            self._stats = torch.zeros(K + K * D, dtype=torch.float32, device=dev)
+        n = K + K * D + (self._restart[1] * D if self._restart is not None else 0)      # counts | dw (| donors [R, D])
+        if self._stats is None or self._stats.device != dev or self._stats.numel() != n:
+            self._stats = torch.zeros(n, dtype=torch.float32, device=dev)
             self._scratch = torch.zeros(K + 2, dtype=torch.float32, device=dev)
         return self._stats, self._scratch
+
+    # ---- dead-code restarts ---------------------------------------------------------------------------------
+    def set_restart(self, patience: Optional[int], max_per_step: int = 32, seed: int = 0):
+        """``patience`` None: off (the ``idle`` and ``restart_total`` buffers go away).  Otherwise a code that no row of any rank chose for ``patience``
+        consecutive training steps is restarted from a row of the current step, at most ``max_per_step`` codes per step."""
+        if patience is not None:
+            check_restart_args(patience, max_per_step)
+            if self.embed_dim % 8:
+                raise NotImplementedError(f"codebook restarts need embed_dim to be a multiple of 8, got {self.embed_dim}")
+        self.wait_ema()
+        for name in ("idle", "restart_total"):
+            if name in self._buffers:
+                del self._buffers[name]
+                self._non_persistent_buffers_set.discard(name)
+        self._restart, self._restart_info = None, None
+        if patience is None:
+            return
+        dev = self.weight.device
+        self._restart = (int(patience), int(max_per_step), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self.register_buffer("idle", torch.zeros(self.n_embed, dtype=torch.int32, device=dev), persistent=False)        # off the state_dict: the keys stay the reference's
+        self.register_buffer("restart_total", torch.zeros(1, dtype=torch.int64, device=dev), persistent=False)
+
+    def restart_info(self) -> Dict[str, object]:
+        """dead codes found, codes restarted and their ids (ascending) in the last training step; ``total``: restarts since the feature was switched on"""
+        if self._restart is None:
+            raise RuntimeError("codebook restarts are off (set_codebook_restart)")
+        if self._restart_info is None:
+            return {"dead": 0, "restarted": 0, "ids": [], "total": int(self.restart_total.item())}
+        self.wait_ema()
+        info = self._restart_info.cpu().tolist()
+        return {"dead": info[0], "restarted": info[1], "ids": info[2:2 + info[1]], "total": int(self.restart_total.item())}
 
     def wait_ema(self):
         """Make the current stream wait for an EMA update still running on the side stream."""
@@ -84,6 +120,40 @@ class Quantizer_impl(nn.Module):
         return out.permute(0, 4, 1, 2, 3)
 
 
+def check_restart_args(patience, max_per_step):
+    """the ranges of ``--codebook_restart_patience`` / ``--codebook_restart_max`` (host only)"""
+    if isinstance(patience, bool) or not isinstance(patience, int) or patience < 1:
+        raise ValueError(f"codebook_restart_patience={patience!r}: an int >= 1 (training steps without an assignment) or None (off) is needed")
+    if isinstance(max_per_step, bool) or not isinstance(max_per_step, int) or not 1 <= max_per_step <= 64:
+        raise ValueError(f"codebook_restart_max={max_per_step!r}: an int in 1..64 (codes restarted per step) is needed")
+
+
+class CodebookRestartState:
+    """What a resumed run needs beyond the network's ``state_dict`` to continue onto the same restarts: the per-code idle counters and the running total
+    (the ``codebook_restart`` entry of ``run_vqvae.py``'s checkpoints; the draw itself is a function of ``--seed`` and the global iteration)."""
+
+    def __init__(self, impl: "Quantizer_impl"):
+        self.impl = impl
+
+    def state_dict(self):
+        q = self.impl
+        if q._restart is None:
+            raise RuntimeError("codebook restarts are off (set_codebook_restart)")
+        q.wait_ema()
+        return {"idle": q.idle.detach().cpu().clone(), "total": int(q.restart_total.item()), "patience": q._restart[0], "max_per_step": q._restart[1]}
+
+    def load_state_dict(self, sd):
+        q = self.impl
+        if q._restart is None:
+            raise RuntimeError("codebook restarts are off (set_codebook_restart)")
+        idle = torch.as_tensor(sd["idle"])
+        if idle.shape != q.idle.shape:
+            raise ValueError(f"codebook_restart: idle counters of {tuple(idle.shape)} codes for a codebook of {tuple(q.idle.shape)}")
+        q.wait_ema()
+        q.idle.copy_(idle.to(device=q.idle.device, dtype=torch.int32))
+        q.restart_total.fill_(int(sd["total"]))
+
+
 class _VQFn(torch.autograd.Function):
     """x [B,D,h,w,d] (any strides) -> (zq_st [B,D,h,w,d], loss, idx [B,h,w,d], perplexity)."""
 
@@ -101,7 +171,7 @@ class _VQFn(torch.autograd.Function):
         stats, scratch = q._work_buffers(dev)
         stats.zero_()
         scratch.zero_()
-        counts, dw = stats[:K], stats[K:]
+        counts, dw = stats[:K], stats[K:K + K * D]
         wnorm, sqerr, ppl = scratch[:K], scratch[K:K + 1], scratch[K + 1:K + 2]
         idx = torch.empty((b, *sp), dtype=torch.int64, device=dev)
         zq = torch.empty_like(rows)
@@ -126,11 +196,30 @@ class _VQFn(torch.autograd.Function):
             ready.record()
             with torch.cuda.stream(q._side):
                 q._side.wait_event(ready)
+                if q._restart is not None:
+                    # donor rows of this step (this rank's part: the others' are zeros here and arrive with the all-reduce below).  Equal M on every
+                    # rank: the sampler pads (utils.general.shard_for_rank), so global row g is local row g mod M of rank g // M
+                    patience, R, seed = q._restart
+                    world = dist.get_world_size(q.process_group) if use_dist else 1
+                    rank = dist.get_rank(q.process_group) if use_dist else 0
+                    donors = stats[K + K * D:]
+                    rows.record_stream(q._side)
+                    _ffi.check(lib.sa_vq_restart_donors(_ffi.ptr(rows), M, D, rank * M, world * M, R, seed, q._restart_step & 0xFFFFFFFFFFFFFFFF,
+                                                        _ffi.ptr(donors), _ffi.stream()), "sa_vq_restart_donors")
                 if use_dist:
                     from ...runtime.ddp import all_reduce_sum
                     all_reduce_sum(stats, q.process_group)
-                _ffi.check(lib.sa_vq_ema_update(_ffi.ptr(q.N), _ffi.ptr(q.embed_avg), _ffi.ptr(cb), _ffi.ptr(counts), _ffi.ptr(dw), K, D, decay, q.eps,
-                                                _ffi.stream()), "sa_vq_ema_update")
+                if q._restart is not None:
+                    if q._restart_info is None or q._restart_info.device != dev:
+                        q._restart_info = torch.zeros(2 + R, dtype=torch.int32, device=dev)
+                    _ffi.check(lib.sa_vq_ema_update_restart(_ffi.ptr(q.N), _ffi.ptr(q.embed_avg), _ffi.ptr(cb), _ffi.ptr(counts), _ffi.ptr(dw), K, D, decay,
+                                                            q.eps, _ffi.ptr(q.idle), patience, _ffi.ptr(donors), min(R, world * M), _ffi.ptr(q._restart_info),
+                                                            _ffi.stream()), "sa_vq_ema_update_restart")
+                    q.restart_total += q._restart_info[1]
+                    q._restart_step += 1
+                else:
+                    _ffi.check(lib.sa_vq_ema_update(_ffi.ptr(q.N), _ffi.ptr(q.embed_avg), _ffi.ptr(cb), _ffi.ptr(counts), _ffi.ptr(dw), K, D, decay, q.eps,
+                                                    _ffi.stream()), "sa_vq_ema_update")
                 done = torch.cuda.Event()
                 done.record()
             q._ema_done = done
@@ -1012,6 +1101,25 @@ class BaselineVQVAE(VQVAEBase, nn.Module):
 
     def get_perplexity(self) -> Sequence[float]:
         return [self.quantizer[0].get_perplexity()]
+
+    # ---------------------------------------------------------------- dead-code restarts (MI355X-only; off by default)
+    def set_codebook_restart(self, patience: Optional[int], max_per_step: int = 32, seed: int = 0) -> None:
+        """Restart codes that no encoder output of any rank chose for ``patience`` consecutive training steps from rows of the current step, at most
+        ``max_per_step`` (1..64) per step; the donor draw is keyed on (``seed``, step).  ``patience=None`` switches the feature off again."""
+        self.quantizer[0].impl.set_restart(patience, max_per_step, seed)
+
+    def set_codebook_restart_step(self, step: int) -> None:
+        """The global iteration of the next training forward (identical on all ranks); without a call the counter advances by one per training forward."""
+        self.quantizer[0].impl._restart_step = int(step)
+
+    def get_codebook_restart_info(self) -> Dict[str, object]:
+        """``{"dead", "restarted", "ids", "total"}`` of the last training step (waits for the side-stream update)."""
+        return self.quantizer[0].impl.restart_info()
+
+    def codebook_restart_state(self) -> CodebookRestartState:
+        """An object with ``state_dict()`` / ``load_state_dict()`` over the idle counters and the running total (a checkpoint entry of its own: the
+        network's ``state_dict`` keeps the reference's keys)."""
+        return CodebookRestartState(self.quantizer[0].impl)
 
     def get_last_layer(self) -> nn.parameter.Parameter:
         if self.use_subpixel_conv:     # (baseline.py:322 would pick the parameter-free AvgPool3d of pad_pool and raise: the conv_block is the last layer with weights)
