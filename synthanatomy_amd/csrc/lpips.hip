@@ -7,8 +7,11 @@
 //                           cover it in a fixed order and accumulates into the volume gradient (no atomics: the slices of a view are distinct)
 //   sa_lpips_maxpool_fwd  : MaxPool2d(3, 2), channels-last, floor extents, first maximum in row-major window order (torch's tie rule), + its argmax
 //   sa_lpips_maxpool_bwd  : the gather form of its gradient, fused with the addend (the LPIPS head's own gradient at that tap) and the ReLU mask
+//   sa_lpips_maxpool_ceil_fwd / _bwd : the same pair with MaxPool2d(3, 2, ceil_mode=True) extents for the LPIPS-squeeze chain:
+//                           the last window may overhang and is clipped to the map.  One kernel pair serves both extent rules
 //   sa_lpips_head         : per tap: unit-normalise both feature maps over channels, d[s] += mean_hw sum_c w_c (f0^ - f1^)^2 and, in the same pass,
 //                           d d / d f1 (the loss-and-gradient-in-one-pass pattern of sa_baur_loss)
+// The slice view and the extent guard are in csrc/lpips_common.h, shared with csrc/lpips_squeeze.hip.
 //
 // THE PADDING RULE.  Upstream scales the image, (u - shift_c) / scale_c, and conv1 then zero-pads the SCALED image: a padded tap contributes 0, not
 // -shift_c / scale_c.  Folding shift and scale into conv1's weights and bias is therefore exact only where the window lies inside the image.  The
@@ -19,25 +22,12 @@
 // THE SUBGRADIENT AT ZERO.  f^ = f / (sqrt(sum_c f^2) + 1e-10).  Where the feature vector of the prediction is all zero, autograd's gradient of
 // the square root is NaN (0 / 0); this kernel takes the subgradient 0 there, i.e. it drops the projection term and writes q / 1e-10, which the ReLU mask
 // of the layer (every f is 0 there) then turns into an exact 0.  A deliberate difference from upstream: the gradient is finite everywhere.
-#include "sa_common.h"
+#include "lpips_common.h"
 
 namespace sa {
 
 constexpr int LP_K = 11, LP_S = 4, LP_P = 2, LP_TAPS = LP_K * LP_K, LP_CLS = 9;
 
-// a 2.5D view of the volume [B, D, H, W]: slice id = b * n + a (a along the view's axis), pixel (i, j) of the slice at b * sb + a * sa + i * si + j * sj
-struct LpView {
-    int32_t n, h, w;
-    int64_t sb, sa, si, sj;
-};
-static bool make_view(int view, int B, int D, int H, int W, LpView& v) {
-    v.sb = (int64_t)D * H * W;
-    if (view == 0) { v.n = D; v.h = H; v.w = W; v.sa = (int64_t)H * W; v.si = W; v.sj = 1; }           // permute (0, 2, 1, 3, 4): [B D, 1, H, W]
-    else if (view == 1) { v.n = H; v.h = D; v.w = W; v.sa = W; v.si = (int64_t)H * W; v.sj = 1; }      // permute (0, 3, 1, 2, 4): [B H, 1, D, W]
-    else if (view == 2) { v.n = W; v.h = D; v.w = H; v.sa = 1; v.si = (int64_t)H * W; v.sj = W; }      // permute (0, 4, 1, 2, 3): [B W, 1, D, H]
-    else return false;
-    return true;
-}
 static inline int conv1_out(int e) { return (e + 2 * LP_P - LP_K) / LP_S + 1; }
 __device__ __forceinline__ int border_class(int o, int e) { return o * LP_S - LP_P < 0 ? 1 : (o * LP_S - LP_P + LP_K - 1 >= e ? 2 : 0); }
 
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(256) void lpips_fold_kernel(const LpFold a) {
 struct LpPool {
     const void* x;          // [S, Hi, Wi, C]
     void* y;                // [S, Ho, Wo, C]
-    unsigned char* idx;     // [S, Ho, Wo, C]: window position 3 * kh + kw of the maximum
+    unsigned char* idx;     // [S, Ho, Wo, C]: position 3 * kh + kw of the maximum, counted in the FULL (unclipped) window under both extent rules
     const void* gy;         // backward: [S, Ho, Wo, C]
     const void* addend;     // backward: [S, Hi, Wi, C] or NULL
     const void* mask;       // backward: [S, Hi, Wi, C] or NULL: gx *= (mask > 0)
@@ -149,8 +139,9 @@ struct LpPool {
     uint64_t total;
 };
 
-// thread = one (output position, channel); lanes run along the channels (coalesced)
-template <typename T>
+// thread = one (output position, channel); lanes run along the channels (coalesced).  CLIP = false: floor extents, 2 * oh + 2 < Hi, every window lies
+// inside the map.  CLIP = true: ceil extents, the last window may overhang and is clipped to the map (it STARTS inside: the extent drops one that would not).
+template <typename T, bool CLIP>
 __global__ __launch_bounds__(256) void lpips_maxpool_fwd_kernel(const LpPool a) {
     const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (e >= a.total) return;
@@ -159,19 +150,23 @@ __global__ __launch_bounds__(256) void lpips_maxpool_fwd_kernel(const LpPool a) 
     const int ow = (int)(p % (uint32_t)a.Wo); p /= (uint32_t)a.Wo;
     const int oh = (int)(p % (uint32_t)a.Ho);
     const int64_t s = (int64_t)(p / (uint32_t)a.Ho);
-    const T* x = (const T*)a.x + ((s * a.Hi + 2 * oh) * a.Wi + 2 * ow) * a.C + c;
+    const int ih = 2 * oh, iw = 2 * ow;
+    const T* x = (const T*)a.x + ((s * a.Hi + ih) * a.Wi + iw) * a.C + c;
     float best = DT<T>::ld(x);
     int arg = 0;
 #pragma unroll
-    for (int k = 1; k < 9; ++k) {       // (2 * oh + 2 < Hi by the floor extents: every window lies inside the map)
-        const float v = DT<T>::ld(x + ((int64_t)(k / 3) * a.Wi + (k % 3)) * a.C);
-        if (v > best || v != v) { best = v; arg = k; }      // strictly greater: the FIRST maximum wins (NaN propagates, as in torch)
+    for (int k = 1; k < 9; ++k) {
+        if (!CLIP || (ih + k / 3 < a.Hi && iw + k % 3 < a.Wi)) {
+            const float v = DT<T>::ld(x + ((int64_t)(k / 3) * a.Wi + (k % 3)) * a.C);
+            if (v > best || v != v) { best = v; arg = k; }      // strictly greater: the FIRST maximum wins (NaN propagates, as in torch)
+        }
     }
     DT<T>::st((T*)a.y + e, best);
     a.idx[e] = (unsigned char)arg;
 }
 
-// thread = one (input position, channel): the <= 2 x 2 windows that contain it, in the order oh, ow.  A trailing row / column no window covers gets 0 (+ addend).
+// thread = one (input position, channel): the <= 2 x 2 windows that contain it, in the order oh, ow (the range is clamped by Ho / Wo, so it serves both
+// extent rules).  Floor extents: a trailing row / column no window covers gets 0 (+ addend).  Ceil extents: every position is covered.
 template <typename T>
 __global__ __launch_bounds__(256) void lpips_maxpool_bwd_kernel(const LpPool a) {
     const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -260,7 +255,53 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const LpHead a) {
     if (threadIdx.x == 0) a.d[s] += (((red[0] + red[1]) + red[2]) + red[3]) * a.inv_p;
 }
 
-static bool lp_ok(int64_t v) { return v > 0 && v < (1ll << 31) - 256; }
+static inline int ceil_pool_out(int e) {
+    int o = (e - 3 + 1) / 2 + 1;        // ceil((e - 3) / 2) + 1 for e >= 2
+    if ((o - 1) * 2 >= e) --o;          // the last window would start outside the map
+    return o;
+}
+
+// floor extents (e - 3) / 2 + 1, sides >= 3; ceil extents as MaxPool2d(ceil_mode=True), sides >= 2
+static int pool_args(LpPool& a, int dtype, int S, int Hi, int Wi, int C, bool ceil, bool bwd) {
+    if (dtype != SA_F32 && dtype != SA_BF16) return SA_EUNSUPPORTED;
+    const int side = ceil ? 2 : 3;
+    if (S <= 0 || Hi < side || Wi < side || C <= 0) return SA_EINVAL;
+    a.Hi = Hi; a.Wi = Wi; a.C = C;
+    a.Ho = ceil ? ceil_pool_out(Hi) : (Hi - 3) / 2 + 1;
+    a.Wo = ceil ? ceil_pool_out(Wi) : (Wi - 3) / 2 + 1;
+    const int64_t tin = (int64_t)S * Hi * Wi * C, tout = (int64_t)S * a.Ho * a.Wo * C;
+    if (tin >= (1ll << 40) || (tin + 255) / 256 >= (1ll << 31)) return SA_EINVAL;
+    a.total = (uint64_t)(bwd ? tin : tout);
+    return 0;
+}
+
+static int pool_fwd(const void* x, int dtype, void* y, void* idx, int S, int Hi, int Wi, int C, bool ceil, void* stream) {
+    if (!x || !y || !idx) return SA_EINVAL;
+    LpPool a = {};
+    const int rc = pool_args(a, dtype, S, Hi, Wi, C, ceil, false);
+    if (rc) return rc;
+    a.x = x; a.y = y; a.idx = (unsigned char*)idx;
+    const dim3 grid((unsigned)((a.total + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (ceil && dtype == SA_F32) SA_LAUNCH((lpips_maxpool_fwd_kernel<float, true>), grid, dim3(256), 0, st, a);
+    else if (ceil) SA_LAUNCH((lpips_maxpool_fwd_kernel<bf16_t, true>), grid, dim3(256), 0, st, a);
+    else if (dtype == SA_F32) SA_LAUNCH((lpips_maxpool_fwd_kernel<float, false>), grid, dim3(256), 0, st, a);
+    else SA_LAUNCH((lpips_maxpool_fwd_kernel<bf16_t, false>), grid, dim3(256), 0, st, a);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+static int pool_bwd(const void* gy, const void* idx, const void* addend, const void* mask, int dtype, void* gx, int S, int Hi, int Wi, int C, bool ceil,
+                    void* stream) {
+    if (!gy || !idx || !gx) return SA_EINVAL;
+    LpPool a = {};
+    const int rc = pool_args(a, dtype, S, Hi, Wi, C, ceil, true);
+    if (rc) return rc;
+    a.gy = gy; a.idx = (unsigned char*)idx; a.addend = addend; a.mask = mask; a.gx = gx;
+    LP_LAUNCH_T(dtype, lpips_maxpool_bwd_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
 
 }  // namespace sa
 
@@ -270,7 +311,7 @@ extern "C" int sa_lpips_unfold(const float* x, int dtype, void* cols, const int3
     if (!x || !cols || !slice_ids) return SA_EINVAL;
     if (dtype != SA_F32 && dtype != SA_BF16) return SA_EUNSUPPORTED;
     LpUnfold a = {};
-    if (S <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || !make_view(view, B, D, H, W, a.v)) return SA_EINVAL;
+    if (S <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || !make_view(view, D, H, W, a.v)) return SA_EINVAL;
     const int sz = dtype == SA_F32 ? 4 : 2;
     if (ld < LP_TAPS + LP_CLS || ((int64_t)ld * sz) % 16 || (int64_t)ld * sz / 16 > 256) return SA_EINVAL;
     if (a.v.h < LP_K - 2 * LP_P || a.v.w < LP_K - 2 * LP_P) return SA_EINVAL;
@@ -285,9 +326,7 @@ extern "C" int sa_lpips_unfold(const float* x, int dtype, void* cols, const int3
     a.dWo = make_fastdiv((uint32_t)a.wo); a.dHo = make_fastdiv((uint32_t)a.ho); a.dCh = make_fastdiv(a.chunks);
     uint64_t blocks = ((uint64_t)rows + a.rpb - 1) / a.rpb;
     if (blocks > 16384u) blocks = 16384u;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SA_F32) SA_LAUNCH(lpips_unfold_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    else SA_LAUNCH(lpips_unfold_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    LP_LAUNCH_T(dtype, lpips_unfold_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     SA_CHECK_LAUNCH();
     return 0;
 }
@@ -297,7 +336,7 @@ extern "C" int sa_lpips_fold(const float* dcols, float* grad, const int32_t* sli
     using namespace sa;
     if (!dcols || !grad || !slice_ids) return SA_EINVAL;
     LpFold a = {};
-    if (S <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || !make_view(view, B, D, H, W, a.v)) return SA_EINVAL;
+    if (S <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || !make_view(view, D, H, W, a.v)) return SA_EINVAL;
     if (ld < LP_TAPS || a.v.h < LP_K - 2 * LP_P || a.v.w < LP_K - 2 * LP_P) return SA_EINVAL;
     a.ho = conv1_out(a.v.h); a.wo = conv1_out(a.v.w);
     const int64_t total = (int64_t)S * a.v.h * a.v.w;
@@ -311,44 +350,22 @@ extern "C" int sa_lpips_fold(const float* dcols, float* grad, const int32_t* sli
     return 0;
 }
 
-static int lpips_pool_args(sa::LpPool& a, int dtype, int S, int Hi, int Wi, int C, bool bwd) {
-    if (dtype != SA_F32 && dtype != SA_BF16) return SA_EUNSUPPORTED;
-    if (S <= 0 || Hi < 3 || Wi < 3 || C <= 0) return SA_EINVAL;
-    a.Hi = Hi; a.Wi = Wi; a.C = C;
-    a.Ho = (Hi - 3) / 2 + 1; a.Wo = (Wi - 3) / 2 + 1;
-    const int64_t tin = (int64_t)S * Hi * Wi * C, tout = (int64_t)S * a.Ho * a.Wo * C;
-    if (tin >= (1ll << 40) || (tin + 255) / 256 >= (1ll << 31)) return SA_EINVAL;
-    a.total = (uint64_t)(bwd ? tin : tout);
-    return 0;
-}
-
 extern "C" int sa_lpips_maxpool_fwd(const void* x, int dtype, void* y, void* idx, int S, int Hi, int Wi, int C, void* stream) {
-    using namespace sa;
-    if (!x || !y || !idx) return SA_EINVAL;
-    LpPool a = {};
-    const int rc = lpips_pool_args(a, dtype, S, Hi, Wi, C, false);
-    if (rc) return rc;
-    a.x = x; a.y = y; a.idx = (unsigned char*)idx;
-    const dim3 grid((unsigned)((a.total + 255) / 256));
-    if (dtype == SA_F32) SA_LAUNCH(lpips_maxpool_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(lpips_maxpool_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    SA_CHECK_LAUNCH();
-    return 0;
+    return sa::pool_fwd(x, dtype, y, idx, S, Hi, Wi, C, false, stream);
 }
 
 extern "C" int sa_lpips_maxpool_bwd(const void* gy, const void* idx, const void* addend, const void* mask, int dtype, void* gx, int S, int Hi, int Wi, int C,
                                     void* stream) {
-    using namespace sa;
-    if (!gy || !idx || !gx) return SA_EINVAL;
-    LpPool a = {};
-    const int rc = lpips_pool_args(a, dtype, S, Hi, Wi, C, true);
-    if (rc) return rc;
-    a.gy = gy; a.idx = (unsigned char*)idx; a.addend = addend; a.mask = mask; a.gx = gx;
-    const dim3 grid((unsigned)((a.total + 255) / 256));
-    if (dtype == SA_F32) SA_LAUNCH(lpips_maxpool_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(lpips_maxpool_bwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    SA_CHECK_LAUNCH();
-    return 0;
+    return sa::pool_bwd(gy, idx, addend, mask, dtype, gx, S, Hi, Wi, C, false, stream);
+}
+
+extern "C" int sa_lpips_maxpool_ceil_fwd(const void* x, int dtype, void* y, void* idx, int S, int Hi, int Wi, int C, void* stream) {
+    return sa::pool_fwd(x, dtype, y, idx, S, Hi, Wi, C, true, stream);
+}
+
+extern "C" int sa_lpips_maxpool_ceil_bwd(const void* gy, const void* idx, const void* addend, const void* mask, int dtype, void* gx, int S, int Hi, int Wi,
+                                         int C, void* stream) {
+    return sa::pool_bwd(gy, idx, addend, mask, dtype, gx, S, Hi, Wi, C, true, stream);
 }
 
 extern "C" int sa_lpips_head(const void* f0, const void* f1, int dtype, const float* w, int S, int P, int C, float* d, void* g1, int relu_mask, void* stream) {
@@ -361,8 +378,7 @@ extern "C" int sa_lpips_head(const void* f0, const void* f1, int dtype, const fl
     a.f0 = f0; a.f1 = f1; a.w = w; a.d = d; a.g1 = g1;
     a.P = P; a.C = C; a.relu_mask = relu_mask;
     a.inv_p = 1.f / (float)P;
-    if (dtype == SA_F32) SA_LAUNCH(lpips_head_kernel<float>, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(lpips_head_kernel<bf16_t>, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, a);
+    LP_LAUNCH_T(dtype, lpips_head_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, a);
     SA_CHECK_LAUNCH();
     return 0;
 }

@@ -1,36 +1,20 @@
-// The memory-bound kernels that the LPIPS-squeeze chain (BaselineLoss of the reference, src/losses/vqvae/vqvae.py:1648-1780, and lpips_kwargs net="squeeze";
-// DESIGN.md section 7.13) needs beyond those of csrc/lpips.hip.  The Fire modules run on the MFMA implicit-GEMM sa_conv_fprop and the seven taps go through
-// sa_lpips_head; these kernels are the two ends and the pools of SqueezeNet-1.1:
+// The two ends of the LPIPS-squeeze chain (BaselineLoss of the reference, src/losses/vqvae/vqvae.py:1648-1780, and lpips_kwargs net="squeeze"; DESIGN.md
+// section 7.13): the first layer of SqueezeNet-1.1 and its adjoint.  The Fire modules run on the MFMA implicit-GEMM sa_conv_fprop, the seven taps go through
+// sa_lpips_head, and the ceil-mode pools (sa_lpips_maxpool_ceil_fwd / _bwd) share their kernels with the floor-mode pair in csrc/lpips.hip; the slice view
+// and the extent guard are in csrc/lpips_common.h.
 //   sa_lpips_squeeze_conv1_fwd : Conv(3 -> 64, k3, s2, p0) + ReLU of the scaled, channel-broadcast slice, read straight from the fp32 volume by (view, slice
 //                                id) like sa_lpips_unfold, written channels-last [S, h1, w1, 64].  The scaling layer is folded into the caller's [9][64]
 //                                weights and bias; with no padding the fold is exact everywhere (no border classes).  Cin = 1 x 9 taps is a bandwidth kernel:
 //                                a slice is read once (L2 serves the overlapping windows), 64 channels are written per position.
 //   sa_lpips_squeeze_conv1_bwd : its adjoint: one thread per voxel of the kept slices sums the <= 2 x 2 covering positions x 64 channels in a fixed order,
 //                                applies the tap's ReLU mask, scales and ACCUMULATES into the fp32 volume gradient (no atomics: the ids are distinct)
-//   sa_lpips_maxpool_ceil_fwd  : MaxPool2d(3, 2, ceil_mode=True), channels-last: the last window may overhang and is clipped to the map; first maximum in
-//                                row-major order of the FULL window (index 3 kh + kw), as sa_lpips_maxpool_fwd
-//   sa_lpips_maxpool_ceil_bwd  : the gather form of its gradient with addend and ReLU mask, as sa_lpips_maxpool_bwd
-#include "sa_common.h"
+#include "lpips_common.h"
 
 namespace sa {
 
 constexpr int SQ_K = 3, SQ_S = 2, SQ_TAPS = 9, SQ_C = 64;
 
-// a 2.5D view of the volume [B, D, H, W] (the views of csrc/lpips.hip): slice id = b * n + a, pixel (i, j) at b * sb + a * sa + i * si + j * sj
-struct SqView {
-    int32_t n, h, w;
-    int64_t sb, sa, si, sj;
-};
-static bool sq_make_view(int view, int D, int H, int W, SqView& v) {
-    v.sb = (int64_t)D * H * W;
-    if (view == 0) { v.n = D; v.h = H; v.w = W; v.sa = (int64_t)H * W; v.si = W; v.sj = 1; }
-    else if (view == 1) { v.n = H; v.h = D; v.w = W; v.sa = W; v.si = (int64_t)H * W; v.sj = 1; }
-    else if (view == 2) { v.n = W; v.h = D; v.w = H; v.sa = 1; v.si = (int64_t)H * W; v.sj = W; }
-    else return false;
-    return true;
-}
 static inline int sq_conv1_out(int e) { return (e - SQ_K) / SQ_S + 1; }
-static bool sq_ok(int64_t v) { return v > 0 && v < (1ll << 31) - 256; }
 
 struct SqConv1 {
     const float* x;         // forward: the fp32 volume
@@ -41,7 +25,7 @@ struct SqConv1 {
     const void* mask;       // backward: [S, ho, wo, 64] T or NULL: the tap itself; gy counts where mask > 0
     float* grad;            // backward: [B, D, H, W] fp32, accumulated
     const int32_t* ids;
-    SqView v;
+    LpView v;
     int32_t S, B, ho, wo, normalize;
     float scale;
     uint32_t total;
@@ -133,91 +117,16 @@ __global__ __launch_bounds__(256) void squeeze_conv1_bwd_kernel(const SqConv1 a)
     *g += a.scale * sum;
 }
 
-struct SqPool {
-    const void* x;          // [S, Hi, Wi, C]
-    void* y;                // [S, Ho, Wo, C]
-    unsigned char* idx;     // [S, Ho, Wo, C]: position 3 * kh + kw of the maximum in the FULL (unclipped) window
-    const void* gy;         // backward: [S, Ho, Wo, C]
-    const void* addend;     // backward: [S, Hi, Wi, C] or NULL
-    const void* mask;       // backward: [S, Hi, Wi, C] or NULL: gx *= (mask > 0)
-    void* gx;               // backward: [S, Hi, Wi, C]
-    int32_t Hi, Wi, Ho, Wo, C;
-    uint64_t total;
-};
-
-// thread = one (output position, channel); lanes run along the channels (coalesced)
-template <typename T>
-__global__ __launch_bounds__(256) void maxpool_ceil_fwd_kernel(const SqPool a) {
-    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (e >= a.total) return;
-    const int c = (int)(e % (uint32_t)a.C);
-    uint64_t p = e / (uint32_t)a.C;
-    const int ow = (int)(p % (uint32_t)a.Wo); p /= (uint32_t)a.Wo;
-    const int oh = (int)(p % (uint32_t)a.Ho);
-    const int64_t s = (int64_t)(p / (uint32_t)a.Ho);
-    const int ih = 2 * oh, iw = 2 * ow;     // (inside the map: the extent drops a window that would START outside)
-    const T* x = (const T*)a.x + ((s * a.Hi + ih) * a.Wi + iw) * a.C + c;
-    float best = DT<T>::ld(x);
-    int arg = 0;
-#pragma unroll
-    for (int k = 1; k < 9; ++k) {
-        if (ih + k / 3 < a.Hi && iw + k % 3 < a.Wi) {       // the last window is clipped to the map
-            const float v = DT<T>::ld(x + ((int64_t)(k / 3) * a.Wi + (k % 3)) * a.C);
-            if (v > best || v != v) { best = v; arg = k; }      // strictly greater: the FIRST maximum wins (NaN propagates, as in torch)
-        }
-    }
-    DT<T>::st((T*)a.y + e, best);
-    a.idx[e] = (unsigned char)arg;
-}
-
-// thread = one (input position, channel): the <= 2 x 2 windows that contain it, in the order oh, ow.  With ceil extents every position is covered.
-template <typename T>
-__global__ __launch_bounds__(256) void maxpool_ceil_bwd_kernel(const SqPool a) {
-    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (e >= a.total) return;
-    const int c = (int)(e % (uint32_t)a.C);
-    uint64_t p = e / (uint32_t)a.C;
-    const int iw = (int)(p % (uint32_t)a.Wi); p /= (uint32_t)a.Wi;
-    const int ih = (int)(p % (uint32_t)a.Hi);
-    const int64_t s = (int64_t)(p / (uint32_t)a.Hi);
-    float sum = a.addend ? DT<T>::ld((const T*)a.addend + e) : 0.f;
-    const int oh_lo = max((ih - 1) / 2, 0), oh_hi = min(ih / 2, a.Ho - 1), ow_lo = max((iw - 1) / 2, 0), ow_hi = min(iw / 2, a.Wo - 1);
-    for (int oh = oh_lo; oh <= oh_hi; ++oh)
-        for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-            const int64_t o = ((s * a.Ho + oh) * a.Wo + ow) * a.C + c;
-            if ((int)a.idx[o] == (ih - 2 * oh) * 3 + (iw - 2 * ow)) sum += DT<T>::ld((const T*)a.gy + o);
-        }
-    if (a.mask && !(DT<T>::ld((const T*)a.mask + e) > 0.f)) sum = 0.f;
-    DT<T>::st((T*)a.gx + e, sum);
-}
-
-static inline int ceil_pool_out(int e) {
-    int o = (e - 3 + 1) / 2 + 1;        // ceil((e - 3) / 2) + 1 for e >= 2
-    if ((o - 1) * 2 >= e) --o;          // the last window would start outside the map
-    return o;
-}
-
 static int sq_conv1_args(SqConv1& a, int dtype, int S, int view, int B, int D, int H, int W, bool bwd) {
-    if (S <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || !sq_make_view(view, D, H, W, a.v)) return SA_EINVAL;
+    if (S <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || !make_view(view, D, H, W, a.v)) return SA_EINVAL;
     if (dtype != SA_F32 && dtype != SA_BF16) return SA_EUNSUPPORTED;
     if (a.v.h < SQ_K || a.v.w < SQ_K) return SA_EINVAL;
     a.ho = sq_conv1_out(a.v.h); a.wo = sq_conv1_out(a.v.w);
     const int64_t pos = (int64_t)S * a.ho * a.wo, vox = (int64_t)S * a.v.h * a.v.w;
-    if (!sq_ok(pos * 8) || !sq_ok(vox) || !sq_ok((int64_t)B * D * H * W) || !sq_ok((int64_t)B * a.v.n)) return SA_EINVAL;
+    if (!lp_ok(pos * 8) || !lp_ok(vox) || !lp_ok((int64_t)B * D * H * W) || !lp_ok((int64_t)B * a.v.n)) return SA_EINVAL;
     a.S = S; a.B = B;
     a.total = (uint32_t)(bwd ? vox : pos * 8);
     a.dA = make_fastdiv((uint32_t)(bwd ? a.v.w : a.wo)); a.dB = make_fastdiv((uint32_t)(bwd ? a.v.h : a.ho));
-    return 0;
-}
-
-static int sq_pool_args(SqPool& a, int dtype, int S, int Hi, int Wi, int C, bool bwd) {
-    if (dtype != SA_F32 && dtype != SA_BF16) return SA_EUNSUPPORTED;
-    if (S <= 0 || Hi < 2 || Wi < 2 || C <= 0) return SA_EINVAL;
-    a.Hi = Hi; a.Wi = Wi; a.C = C;
-    a.Ho = ceil_pool_out(Hi); a.Wo = ceil_pool_out(Wi);
-    const int64_t tin = (int64_t)S * Hi * Wi * C, tout = (int64_t)S * a.Ho * a.Wo * C;
-    if (tin >= (1ll << 40) || (tin + 255) / 256 >= (1ll << 31)) return SA_EINVAL;
-    a.total = (uint64_t)(bwd ? tin : tout);
     return 0;
 }
 
@@ -232,8 +141,7 @@ extern "C" int sa_lpips_squeeze_conv1_fwd(const float* x, int dtype, const float
     if (rc) return rc;
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.ids = slice_ids; a.normalize = normalize;
     const dim3 grid((a.total + 255u) / 256u);
-    if (dtype == SA_F32) SA_LAUNCH(squeeze_conv1_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(squeeze_conv1_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    LP_LAUNCH_T(dtype, squeeze_conv1_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
     SA_CHECK_LAUNCH();
     return 0;
 }
@@ -247,37 +155,7 @@ extern "C" int sa_lpips_squeeze_conv1_bwd(const void* gy, const void* mask, int 
     if (rc) return rc;
     a.gy = gy; a.mask = mask; a.w = w; a.grad = grad; a.ids = slice_ids; a.scale = scale;
     const dim3 grid((a.total + 255u) / 256u);
-    if (dtype == SA_F32) SA_LAUNCH(squeeze_conv1_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(squeeze_conv1_bwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    SA_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sa_lpips_maxpool_ceil_fwd(const void* x, int dtype, void* y, void* idx, int S, int Hi, int Wi, int C, void* stream) {
-    using namespace sa;
-    if (!x || !y || !idx) return SA_EINVAL;
-    SqPool a = {};
-    const int rc = sq_pool_args(a, dtype, S, Hi, Wi, C, false);
-    if (rc) return rc;
-    a.x = x; a.y = y; a.idx = (unsigned char*)idx;
-    const dim3 grid((unsigned)((a.total + 255) / 256));
-    if (dtype == SA_F32) SA_LAUNCH(maxpool_ceil_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(maxpool_ceil_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    SA_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sa_lpips_maxpool_ceil_bwd(const void* gy, const void* idx, const void* addend, const void* mask, int dtype, void* gx, int S, int Hi, int Wi,
-                                         int C, void* stream) {
-    using namespace sa;
-    if (!gy || !idx || !gx) return SA_EINVAL;
-    SqPool a = {};
-    const int rc = sq_pool_args(a, dtype, S, Hi, Wi, C, true);
-    if (rc) return rc;
-    a.gy = gy; a.idx = (unsigned char*)idx; a.addend = addend; a.mask = mask; a.gx = gx;
-    const dim3 grid((unsigned)((a.total + 255) / 256));
-    if (dtype == SA_F32) SA_LAUNCH(maxpool_ceil_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else SA_LAUNCH(maxpool_ceil_bwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    LP_LAUNCH_T(dtype, squeeze_conv1_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
     SA_CHECK_LAUNCH();
     return 0;
 }

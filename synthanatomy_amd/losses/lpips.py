@@ -43,31 +43,33 @@ def expected_shapes() -> Dict[str, Tuple[int, ...]]:
     return shapes
 
 
-def random_state_dict(seed: int) -> Dict[str, torch.Tensor]:
-    """Seeded stand-in weights in the key layout of ``lpips.LPIPS(net='alex').state_dict()``: He-scaled convolutions, small biases, NON-NEGATIVE lin
-    weights (as the trained ones are).  For tests, smoke runs and benchmarks only -- the distances mean nothing."""
+def _draw_state_dict(seed: int, shapes: Dict[str, Tuple[int, ...]]) -> Dict[str, torch.Tensor]:
+    """one seeded draw in the order of ``shapes``: He-scaled convolutions, small biases, NON-NEGATIVE lin weights (as the trained ones are)"""
     gen = torch.Generator().manual_seed(int(seed))
     sd = {}
-    for key, (ci, co, k, _, _) in zip(CONV_KEYS, ALEX_CONVS):
-        sd[key + ".weight"] = torch.randn(co, ci, k, k, generator=gen, dtype=torch.float64).mul_((2.0 / (ci * k * k)) ** 0.5).float()
-        sd[key + ".bias"] = torch.randn(co, generator=gen, dtype=torch.float64).mul_(0.1).float()
-    for key, (_, co, _, _, _) in zip(LIN_KEYS, ALEX_CONVS):
-        sd[key] = torch.rand(1, co, 1, 1, generator=gen, dtype=torch.float64).float()
+    for key, shape in shapes.items():
+        if key.startswith("lin"):
+            sd[key] = torch.rand(shape, generator=gen, dtype=torch.float64).float()
+        elif key.endswith(".weight"):
+            fan = shape[1] * shape[2] * shape[3]
+            sd[key] = torch.randn(shape, generator=gen, dtype=torch.float64).mul_((2.0 / fan) ** 0.5).float()
+        else:
+            sd[key] = torch.randn(shape, generator=gen, dtype=torch.float64).mul_(0.1).float()
     return sd
 
 
-def validate_state_dict(sd, source: str) -> Dict[str, torch.Tensor]:
-    """The tensors this build needs from an LPIPS-alex state dict, checked by name and shape (``ValueError`` naming the key)."""
+def _validate_layout(sd, source: str, shapes: Dict[str, Tuple[int, ...]], net: str, tool: str, foreign_keys: Sequence[str], foreign: str):
+    """The tensors of ``shapes`` from a state dict, checked by name and shape (``ValueError`` naming the key), + the scaling layer (the published constants
+    when the file has none).  A file that holds one of ``foreign_keys`` belongs to the other network and is refused with ``foreign``."""
     if not isinstance(sd, dict):
         raise ValueError(f"--perceptual_weights {source}: expected a torch.save'd dict of tensors, got {type(sd).__name__}")
-    if "net.slice2.3.squeeze.weight" in sd:
-        raise ValueError(f"--perceptual_weights {source}: this is an LPIPS-squeeze file (it holds 'net.slice2.3.squeeze.weight'); it serves --loss=baseline "
-                         "and lpips_kwargs net='squeeze', not the LPIPS-alex losses")
+    if any(key in sd for key in foreign_keys):
+        raise ValueError(f"--perceptual_weights {source}: {foreign}")
     out = {}
-    for key, shape in expected_shapes().items():
+    for key, shape in shapes.items():
         if key not in sd:
-            raise ValueError(f"--perceptual_weights {source}: key {key!r} is missing (expected the layout of lpips.LPIPS(net='alex').state_dict(); "
-                             f"tools/make_lpips_weights.py builds it from the two upstream files)")
+            raise ValueError(f"--perceptual_weights {source}: key {key!r} is missing (expected the layout of lpips.LPIPS(net={net!r}).state_dict(); "
+                             f"{tool} builds it from the two upstream files)")
         t = sd[key]
         if not torch.is_tensor(t) or tuple(t.shape) != shape:
             raise ValueError(f"--perceptual_weights {source}: {key!r} has shape {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}, expected {shape}")
@@ -81,6 +83,19 @@ def validate_state_dict(sd, source: str) -> Dict[str, torch.Tensor]:
         else:
             out[key] = torch.tensor(default, dtype=torch.float64)
     return out
+
+
+def random_state_dict(seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in weights in the key layout of ``lpips.LPIPS(net='alex').state_dict()``.  For tests, smoke runs and benchmarks only -- the distances
+    mean nothing."""
+    return _draw_state_dict(seed, expected_shapes())
+
+
+def validate_state_dict(sd, source: str) -> Dict[str, torch.Tensor]:
+    """The tensors this build needs from an LPIPS-alex state dict; an LPIPS-squeeze file is refused as such."""
+    return _validate_layout(sd, source, expected_shapes(), "alex", "tools/make_lpips_weights.py", ("net.slice2.3.squeeze.weight",),
+                            "this is an LPIPS-squeeze file (it holds 'net.slice2.3.squeeze.weight'); it serves --loss=baseline "
+                            "and lpips_kwargs net='squeeze', not the LPIPS-alex losses")
 
 
 def load_weights(spec: str, net: str = "alex") -> Dict[str, torch.Tensor]:
@@ -125,6 +140,18 @@ def conv1_extent(e: int) -> int:
 
 def pool_extent(e: int) -> int:
     return (e - 3) // 2 + 1
+
+
+def ceil_pool_extent(e: int) -> int:
+    """MaxPool2d(3, 2, ceil_mode=True): ceil((e - 3) / 2) + 1, minus one if the last window would start outside the input"""
+    o = -(-(e - 3) // 2) + 1
+    return o - 1 if (o - 1) * 2 >= e else o
+
+
+def slice_sides(shape, view: int) -> Tuple[int, int]:
+    """(h, w) of the slices of one 2.5D view of a volume [B, 1, D, H, W]"""
+    _, _, D, H, W = shape
+    return ((H, W), (D, W), (D, H))[view]
 
 
 def folded_conv1(w: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, h: int, w_: int) -> torch.Tensor:
@@ -209,16 +236,76 @@ class Conv2dOp:
         return out
 
 
-class LpipsAlex(torch.nn.Module):
-    """Frozen LPIPS-alex weights as NON-PERSISTENT buffers (no Parameter: nothing reaches an optimiser, a gradient reducer or a checkpoint) and the
-    launch chain of the perceptual term over the kept slices of one view."""
+class LpipsNet(torch.nn.Module):
+    """What the LPIPS networks of this build share: the compute dtype, the workspace cap, the operator cache, the two pool launches and the frame of
+    ``view_term`` -- chunking, the distance accumulator and the head launches.  A network adds its frozen weights as NON-PERSISTENT buffers (no Parameter:
+    nothing reaches an optimiser, a gradient reducer or a checkpoint) with ``lin0 .. lin{T-1}`` for its T taps, and
 
-    def __init__(self, weights: Dict[str, torch.Tensor], compute_dtype: torch.dtype = torch.float32, workspace_cap: int = WORKSPACE_CAP):
+    * ``bytes_per_slice(h, w, esize)``: activations of both images + gradients of one, per kept slice (the chunk size follows from the workspace cap);
+    * ``_features(y, y_pred, view, cid, normalize) -> (taps, saved)``: the tap feature maps [2 S, h, w, C] of one chunk -- target slices in the first
+      half, the prediction's in the second -- and whatever ``_input_grad`` needs besides them;
+    * ``_input_grad(gh, taps, saved, grad, view, cid, scale)``: grad += scale * (the heads' gradients ``gh`` at the prediction's taps, carried back to
+      the kept slices ``cid`` of the volume)."""
+
+    def __init__(self, compute_dtype: torch.dtype, workspace_cap: int):
         super().__init__()
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise NotImplementedError(f"LPIPS compute dtype must be float32 (parity) or bfloat16 (throughput); got {compute_dtype}")
         self.compute_dtype = compute_dtype
         self.workspace_cap = int(workspace_cap)
+        self._ops = {}
+
+    def _pool(self, x: torch.Tensor, ceil: bool):
+        """MaxPool2d(3, 2, ceil_mode=ceil) of channels-last [N, hi, wi, C] and its argmax (uint8)"""
+        N, hi, wi, C = x.shape
+        extent, fn = (ceil_pool_extent, "sa_lpips_maxpool_ceil_fwd") if ceil else (pool_extent, "sa_lpips_maxpool_fwd")
+        p = torch.empty((N, extent(hi), extent(wi), C), dtype=x.dtype, device=x.device)
+        idx = torch.empty(p.shape, dtype=torch.uint8, device=x.device)
+        _ffi.check(getattr(_ffi.lib(), fn)(_ffi.ptr(x), _ffi.dtype_id(x.dtype), _ffi.ptr(p), _ffi.ptr(idx), N, hi, wi, C, _ffi.stream()), fn)
+        return p, idx
+
+    def _unpool(self, gp: torch.Tensor, idx: torch.Tensor, addend: Optional[torch.Tensor], mask: Optional[torch.Tensor], shape, ceil: bool) -> torch.Tensor:
+        """gradient at a pool's input [S, hi, wi, C] from the gradient at its output: (addend + the routed gp) * (mask > 0)"""
+        _, hi, wi, C = shape
+        fn = "sa_lpips_maxpool_ceil_bwd" if ceil else "sa_lpips_maxpool_bwd"
+        gx = torch.empty((gp.shape[0], hi, wi, C), dtype=gp.dtype, device=gp.device)
+        _ffi.check(getattr(_ffi.lib(), fn)(_ffi.ptr(gp), ctypes.c_void_p(idx.data_ptr()), _ffi.ptr(addend),
+                                           ctypes.c_void_p(mask.data_ptr()) if mask is not None else None, _ffi.dtype_id(gp.dtype), _ffi.ptr(gx),
+                                           gp.shape[0], hi, wi, C, _ffi.stream()), fn)
+        return gx
+
+    def view_term(self, y: torch.Tensor, y_pred: torch.Tensor, view: int, ids: torch.Tensor, grad: Optional[torch.Tensor], scale: float,
+                  normalize: bool, chunk: Optional[int] = None) -> torch.Tensor:
+        """d [S] fp32 = LPIPS(y slice, y_pred slice) for the kept slices ``ids`` (device int32) of ``view``; when ``grad`` (fp32 volume) is given,
+        grad += scale * d sum(d) / d y_pred.  Per chunk: the network's forward launches, one head per tap and, with a gradient, its backward launches
+        (the networks' ``_features`` give the counts)."""
+        h, w = slice_sides(y.shape, view)
+        d = torch.zeros(ids.numel(), dtype=torch.float32, device=y.device)
+        if chunk is None:
+            chunk = max(1, self.workspace_cap // self.bytes_per_slice(h, w, 2 if self.compute_dtype == torch.bfloat16 else 4))
+        for lo in range(0, ids.numel(), chunk):      # (a call per chunk: its workspace is released before the next chunk allocates)
+            self._chunk_term(y, y_pred, view, ids[lo:lo + chunk], d[lo:lo + chunk], grad, float(scale) * (2.0 if normalize else 1.0), normalize)
+        return d
+
+    def _chunk_term(self, y, y_pred, view, cid, dc, grad, scale, normalize):
+        S, dt = cid.numel(), self.compute_dtype
+        taps, saved = self._features(y, y_pred, view, cid, normalize)
+        gh = []
+        for l, f in enumerate(taps):
+            _, hl, wl, C = f.shape
+            g1 = torch.empty((S, hl, wl, C), dtype=dt, device=y.device) if grad is not None else None
+            _ffi.check(_ffi.lib().sa_lpips_head(_ffi.ptr(f), ctypes.c_void_p(f[S:].data_ptr()), _ffi.dtype_id(dt), _ffi.ptr(getattr(self, f"lin{l}")), S, hl * wl,
+                                                C, _ffi.ptr(dc), _ffi.ptr(g1), int(l == len(taps) - 1), _ffi.stream()), "sa_lpips_head")
+            gh.append(g1)
+        if grad is not None:
+            self._input_grad(gh, taps, saved, grad, view, cid, scale)
+
+
+class LpipsAlex(LpipsNet):
+    """Frozen LPIPS-alex weights and the launch chain of the perceptual term over the kept slices of one view."""
+
+    def __init__(self, weights: Dict[str, torch.Tensor], compute_dtype: torch.dtype = torch.float32, workspace_cap: int = WORKSPACE_CAP):
+        super().__init__(compute_dtype, workspace_cap)
         for i, key in enumerate(CONV_KEYS):
             self.register_buffer(f"w{i}", weights[key + ".weight"].float().clone(), persistent=False)
             self.register_buffer(f"b{i}", weights[key + ".bias"].float().clone(), persistent=False)
@@ -226,7 +313,6 @@ class LpipsAlex(torch.nn.Module):
             self.register_buffer(f"lin{i}", weights[key].float().reshape(-1).clone(), persistent=False)
         self.register_buffer("shift", weights["scaling_layer.shift"].double().clone(), persistent=False)
         self.register_buffer("scale", weights["scaling_layer.scale"].double().clone(), persistent=False)
-        self._ops = {}
 
     def _conv(self, i: int, h: int = 0, w: int = 0) -> Conv2dOp:
         """layer i's operator on the buffers' device; conv1 (i = 0) is the folded 1-tap matrix of a slice shape"""
@@ -242,75 +328,64 @@ class LpipsAlex(torch.nn.Module):
             self._ops[key] = op
         return op
 
+    def _convs(self, shape, view: int) -> List[Conv2dOp]:
+        return [self._conv(0, *slice_sides(shape, view))] + [self._conv(i) for i in range(1, 5)]
+
     @staticmethod
     def bytes_per_slice(h: int, w: int, esize: int) -> int:
-        """activations of both images + gradients of one, per kept slice (the chunk size follows from the workspace cap)"""
         h1, w1 = conv1_extent(h), conv1_extent(w)
         h2, w2 = pool_extent(h1), pool_extent(w1)
         h3, w3 = pool_extent(h2), pool_extent(w2)
         act = h1 * w1 * (UNFOLD_LD + 64) + h2 * w2 * (64 + 192) + h3 * w3 * (192 + 384 + 256 + 256)
         return 3 * act * esize + h1 * w1 * UNFOLD_LD * 4 + h2 * w2 * 64 + h3 * w3 * 192
 
-    def view_term(self, y: torch.Tensor, y_pred: torch.Tensor, view: int, ids: torch.Tensor, grad: Optional[torch.Tensor], scale: float,
-                  normalize: bool, chunk: Optional[int] = None) -> torch.Tensor:
-        """d [S] fp32 = LPIPS(y slice, y_pred slice) for the kept slices ``ids`` (device int32) of ``view``; when ``grad`` (fp32 volume) is given,
-        grad += scale * d sum(d) / d y_pred.  Launches per chunk: 1 unfold (both images: 2), 5 GEMM forwards, 2 pools, 5 heads; with a gradient 2 pool
-        backwards, 5 data-gradient GEMMs and 1 fold."""
-        lib, st = _ffi.lib(), _ffi.stream()
+    def _features(self, y, y_pred, view, cid, normalize):
+        """Launches: 1 unfold per image (2), 5 GEMM forwards, 2 pools.  saved = the two pools' argmax maps."""
         B, _, D, H, W = y.shape
-        h, w = ((H, W), (D, W), (D, H))[view]
-        dt, did = self.compute_dtype, _ffi.dtype_id(self.compute_dtype)
-        S_all = ids.numel()
-        d = torch.zeros(S_all, dtype=torch.float32, device=y.device)
-        if chunk is None:
-            chunk = max(1, self.workspace_cap // self.bytes_per_slice(h, w, 2 if dt == torch.bfloat16 else 4))
-        h1, w1 = conv1_extent(h), conv1_extent(w)
-        h2, w2 = pool_extent(h1), pool_extent(w1)
-        h3, w3 = pool_extent(h2), pool_extent(w2)
-        convs = [self._conv(0, h, w)] + [self._conv(i) for i in range(1, 5)]
-        lins = [getattr(self, f"lin{i}") for i in range(5)]
-        for lo in range(0, S_all, chunk):
-            cid = ids[lo:lo + chunk]
-            S = cid.numel()
-            cols = torch.empty((2 * S, h1, w1, UNFOLD_LD), dtype=dt, device=y.device)
-            for half, vol in enumerate((y, y_pred)):
-                _ffi.check(lib.sa_lpips_unfold(_ffi.ptr(vol), did, ctypes.c_void_p(cols[half * S:].data_ptr()), _ffi.ptr(cid), S, view, B, D, H, W, int(normalize),
-                                               UNFOLD_LD, st), "sa_lpips_unfold")
-            f = [convs[0].fprop(cols)]
-            del cols
-            pools = []
-            for i in (1, 2):
-                hi, wi, C = f[-1].shape[1:]
-                p = torch.empty((2 * S, pool_extent(hi), pool_extent(wi), C), dtype=dt, device=y.device)
-                idx = torch.empty(p.shape, dtype=torch.uint8, device=y.device)
-                _ffi.check(lib.sa_lpips_maxpool_fwd(_ffi.ptr(f[-1]), did, _ffi.ptr(p), _ffi.ptr(idx), 2 * S, hi, wi, C, st), "sa_lpips_maxpool_fwd")
-                pools.append(idx)
-                f.append(convs[i].fprop(p))
-            f.append(convs[3].fprop(f[-1]))
-            f.append(convs[4].fprop(f[-1]))
-            dc = d[lo:lo + S]
-            gh = []
-            for l in range(5):
-                _, hl, wl, C = f[l].shape
-                g1 = torch.empty((S, hl, wl, C), dtype=dt, device=y.device) if grad is not None else None
-                _ffi.check(lib.sa_lpips_head(_ffi.ptr(f[l]), ctypes.c_void_p(f[l][S:].data_ptr()), did, _ffi.ptr(lins[l]), S, hl * wl, C, _ffi.ptr(dc), _ffi.ptr(g1),
-                                             int(l == 4), st), "sa_lpips_head")
-                gh.append(g1)
-            if grad is None:
-                continue
-            # data gradients of the prediction's half: each launch adds the head's own gradient at that tap and applies the tap's ReLU mask
-            gz = convs[4].dgrad(gh[4], addend=gh[3], mask=f[3][S:])
-            gz = convs[3].dgrad(gz, addend=gh[2], mask=f[2][S:])
-            for i in (2, 1):
-                gp = convs[i].dgrad(gz)
-                _, hi, wi, C = f[i - 1].shape
-                gz = torch.empty((S, hi, wi, C), dtype=dt, device=y.device)
-                _ffi.check(lib.sa_lpips_maxpool_bwd(_ffi.ptr(gp), ctypes.c_void_p(pools[i - 1][S:].data_ptr()), _ffi.ptr(gh[i - 1]),
-                                                    ctypes.c_void_p(f[i - 1][S:].data_ptr()), did, _ffi.ptr(gz), S, hi, wi, C, st), "sa_lpips_maxpool_bwd")
-            dcols = convs[0].dgrad(gz, out_dtype=torch.float32)
-            _ffi.check(lib.sa_lpips_fold(_ffi.ptr(dcols), _ffi.ptr(grad), _ffi.ptr(cid), S, view, B, D, H, W, float(scale) * (2.0 if normalize else 1.0),
-                                         UNFOLD_LD, st), "sa_lpips_fold")
-        return d
+        S, dt = cid.numel(), self.compute_dtype
+        h, w = slice_sides(y.shape, view)
+        convs = self._convs(y.shape, view)
+        cols = torch.empty((2 * S, conv1_extent(h), conv1_extent(w), UNFOLD_LD), dtype=dt, device=y.device)
+        for half, vol in enumerate((y, y_pred)):
+            _ffi.check(_ffi.lib().sa_lpips_unfold(_ffi.ptr(vol), _ffi.dtype_id(dt), ctypes.c_void_p(cols[half * S:].data_ptr()), _ffi.ptr(cid), S, view, B, D, H, W,
+                                                  int(normalize), UNFOLD_LD, _ffi.stream()), "sa_lpips_unfold")
+        f = [convs[0].fprop(cols)]
+        del cols
+        pools = []
+        for i in (1, 2):
+            p, idx = self._pool(f[-1], ceil=False)
+            pools.append(idx)
+            f.append(convs[i].fprop(p))
+        f.append(convs[3].fprop(f[-1]))
+        f.append(convs[4].fprop(f[-1]))
+        return f, pools
+
+    def _input_grad(self, gh, f, pools, grad, view, cid, scale):
+        """Launches: 5 data-gradient GEMMs, 2 pool backwards, 1 fold.  Data gradients of the prediction's half: each launch adds the head's own gradient at
+        that tap and applies the tap's ReLU mask."""
+        B, _, D, H, W = grad.shape
+        S = cid.numel()
+        convs = self._convs(grad.shape, view)
+        gz = convs[4].dgrad(gh[4], addend=gh[3], mask=f[3][S:])
+        gz = convs[3].dgrad(gz, addend=gh[2], mask=f[2][S:])
+        for i in (2, 1):
+            gz = self._unpool(convs[i].dgrad(gz), pools[i - 1][S:], gh[i - 1], f[i - 1][S:], f[i - 1].shape, ceil=False)
+        dcols = convs[0].dgrad(gz, out_dtype=torch.float32)
+        _ffi.check(_ffi.lib().sa_lpips_fold(_ffi.ptr(dcols), _ffi.ptr(grad), _ffi.ptr(cid), S, view, B, D, H, W, scale, UNFOLD_LD, _ffi.stream()), "sa_lpips_fold")
+
+
+def view_sums(pred: torch.Tensor, target: torch.Tensor, net: LpipsNet, views: Sequence[int], ids: List[torch.Tensor], factor: float, normalize: bool, chunk):
+    """The common part of the loss-and-gradient-in-forward Functions: per view the fp64 sum of the LPIPS distances over its kept slices ``ids`` and, when
+    ``pred`` requires a gradient, grad = d (factor * sum over the views of the mean distance) / d pred (else None).  Returns (grad, sums)."""
+    _ffi.require_gpu()
+    a = pred.contiguous()
+    b = target.contiguous().to(a.device)
+    grad = torch.zeros_like(a) if pred.requires_grad else None
+    sums = []
+    for view, vid in zip(views, ids):
+        d = net.view_term(b, a, view, vid, grad, factor / vid.numel(), normalize, chunk)
+        sums.append(d.double().sum())       # (one fixed-order reduction of <= a few thousand values)
+    return grad, sums
 
 
 class PerceptualFn(torch.autograd.Function):
@@ -318,19 +393,12 @@ class PerceptualFn(torch.autograd.Function):
     pass; returns the differentiable sum and the per-view terms as non-differentiable side outputs (the summaries)."""
 
     @staticmethod
-    def forward(ctx, pred, target, net: LpipsAlex, views: Sequence[int], ids: List[torch.Tensor], factor: float, normalize: bool, chunk):
-        _ffi.require_gpu()
-        a = pred.contiguous()
-        b = target.contiguous().to(a.device)
-        grad = torch.zeros_like(a) if pred.requires_grad else None
-        terms = []
-        for view, vid in zip(views, ids):
-            d = net.view_term(b, a, view, vid, grad, factor / vid.numel(), normalize, chunk)
-            terms.append(d.double().sum().div(vid.numel()).mul(factor).float())     # (one fixed-order reduction of <= a few thousand values)
+    def forward(ctx, pred, target, net: LpipsNet, views: Sequence[int], ids: List[torch.Tensor], factor: float, normalize: bool, chunk):
+        ctx.grad, sums = view_sums(pred, target, net, views, ids, factor, normalize, chunk)
+        terms = [s.div(vid.numel()).mul(factor).float() for s, vid in zip(sums, ids)]
         total = terms[0].clone()
         for t in terms[1:]:
             total = total + t
-        ctx.grad = grad
         ctx.mark_non_differentiable(*terms)
         return (total, *terms)
 

@@ -6,17 +6,18 @@ The arithmetic restates ``lpips.LPIPS(net='squeeze', version='0.1', lpips=True, 
 Conv(3 -> 64, k3, s2, p0) + ReLU [tap 1], three MaxPool(3, 2, ceil_mode=True), eight Fire modules (squeeze 1x1 + ReLU, expand 1x1 and expand 3x3 p1,
 concatenated, + ReLU) with taps after features 4, 7, 9, 10, 11, 12; seven ``lin`` rows; the head and its zero subgradient are those of losses/lpips.py.
 
-Same ``view_term`` contract as :class:`~synthanatomy_amd.losses.lpips.LpipsAlex`, so ``PerceptualFn`` and the loss classes take either network.
+Runs on the ``view_term`` frame of :class:`~synthanatomy_amd.losses.lpips.LpipsNet`, as ``LpipsAlex`` does, so ``PerceptualFn`` and the loss classes take
+either network; weight validation, the seeded draw and the pools are the shared ones of losses/lpips.py.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Optional, Tuple
+from typing import Dict, Tuple
 
 import torch
 
 from .. import _ffi
-from .lpips import SCALE, SHIFT, WORKSPACE_CAP, Conv2dOp
+from .lpips import WORKSPACE_CAP, Conv2dOp, LpipsNet, _draw_state_dict, _validate_layout, ceil_pool_extent, slice_sides  # noqa: F401
 
 # (features index, state-dict prefix, cin, squeeze, expand1x1, expand3x3) of torchvision's squeezenet1_1 inside lpips.LPIPS(net='squeeze')
 FIRES = ((3, "net.slice2.3", 64, 16, 64, 64), (4, "net.slice2.4", 128, 16, 64, 64), (6, "net.slice3.6", 128, 32, 128, 128),
@@ -41,47 +42,16 @@ def expected_shapes() -> Dict[str, Tuple[int, ...]]:
 
 
 def random_state_dict(seed: int) -> Dict[str, torch.Tensor]:
-    """Seeded stand-in weights in the key layout of ``lpips.LPIPS(net='squeeze').state_dict()``: He-scaled convolutions, small biases, NON-NEGATIVE lin
-    weights.  For tests, smoke runs and benchmarks only -- the distances mean nothing."""
-    gen = torch.Generator().manual_seed(int(seed))
-    sd = {}
-    for key, shape in expected_shapes().items():
-        if key in LIN_KEYS:
-            sd[key] = torch.rand(shape, generator=gen, dtype=torch.float64).float()
-        elif key.endswith(".weight"):
-            fan = shape[1] * shape[2] * shape[3]
-            sd[key] = torch.randn(shape, generator=gen, dtype=torch.float64).mul_((2.0 / fan) ** 0.5).float()
-        else:
-            sd[key] = torch.randn(shape, generator=gen, dtype=torch.float64).mul_(0.1).float()
-    return sd
+    """Seeded stand-in weights in the key layout of ``lpips.LPIPS(net='squeeze').state_dict()``.  For tests, smoke runs and benchmarks only -- the
+    distances mean nothing."""
+    return _draw_state_dict(seed, expected_shapes())
 
 
 def validate_state_dict(sd, source: str) -> Dict[str, torch.Tensor]:
-    """The tensors this build needs from an LPIPS-squeeze state dict, checked by name and shape (``ValueError`` naming the key); an LPIPS-alex file is
-    refused as such."""
-    if not isinstance(sd, dict):
-        raise ValueError(f"--perceptual_weights {source}: expected a torch.save'd dict of tensors, got {type(sd).__name__}")
-    if "net.slice4.8.weight" in sd or "net.slice2.3.weight" in sd:
-        raise ValueError(f"--perceptual_weights {source}: this is an LPIPS-alex file (it holds 'net.slice2.3.weight'); --loss=baseline and "
-                         "lpips_kwargs net='squeeze' need the layout of lpips.LPIPS(net='squeeze').state_dict() (tools/make_lpips_weights.py --net=squeeze)")
-    out = {}
-    for key, shape in expected_shapes().items():
-        if key not in sd:
-            raise ValueError(f"--perceptual_weights {source}: key {key!r} is missing (expected the layout of lpips.LPIPS(net='squeeze').state_dict(); "
-                             f"tools/make_lpips_weights.py --net=squeeze builds it from the two upstream files)")
-        t = sd[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != shape:
-            raise ValueError(f"--perceptual_weights {source}: {key!r} has shape {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}, expected {shape}")
-        out[key] = t.detach().float().cpu().contiguous()
-    for key, default in (("scaling_layer.shift", SHIFT), ("scaling_layer.scale", SCALE)):
-        if key in sd:
-            t = sd[key]
-            if not torch.is_tensor(t) or t.numel() != 3:
-                raise ValueError(f"--perceptual_weights {source}: {key!r} must hold 3 values")
-            out[key] = t.detach().double().reshape(3).cpu()
-        else:
-            out[key] = torch.tensor(default, dtype=torch.float64)
-    return out
+    """The tensors this build needs from an LPIPS-squeeze state dict; an LPIPS-alex file is refused as such."""
+    return _validate_layout(sd, source, expected_shapes(), "squeeze", "tools/make_lpips_weights.py --net=squeeze", ("net.slice4.8.weight", "net.slice2.3.weight"),
+                            "this is an LPIPS-alex file (it holds 'net.slice2.3.weight'); --loss=baseline and lpips_kwargs net='squeeze' need the "
+                            "layout of lpips.LPIPS(net='squeeze').state_dict() (tools/make_lpips_weights.py --net=squeeze)")
 
 
 def is_squeeze_layout(weights) -> bool:
@@ -90,12 +60,6 @@ def is_squeeze_layout(weights) -> bool:
 
 def conv1_extent(e: int) -> int:
     return (e - 3) // 2 + 1
-
-
-def ceil_pool_extent(e: int) -> int:
-    """MaxPool2d(3, 2, ceil_mode=True): ceil((e - 3) / 2) + 1, minus one if the last window would start outside the input"""
-    o = -(-(e - 3) // 2) + 1
-    return o - 1 if (o - 1) * 2 >= e else o
 
 
 def extents(e: int, what: str = "slice side") -> Tuple[int, int, int, int]:
@@ -124,15 +88,11 @@ def merged_expand(w1: torch.Tensor, b1: torch.Tensor, w3: torch.Tensor, b3: torc
     return wm, torch.cat([b1, b3])
 
 
-class LpipsSqueeze(torch.nn.Module):
-    """Frozen LPIPS-squeeze weights as NON-PERSISTENT buffers and the launch chain of the perceptual term over the kept slices of one view."""
+class LpipsSqueeze(LpipsNet):
+    """Frozen LPIPS-squeeze weights and the launch chain of the perceptual term over the kept slices of one view."""
 
     def __init__(self, weights: Dict[str, torch.Tensor], compute_dtype: torch.dtype = torch.float32, workspace_cap: int = WORKSPACE_CAP):
-        super().__init__()
-        if compute_dtype not in (torch.float32, torch.bfloat16):
-            raise NotImplementedError(f"LPIPS compute dtype must be float32 (parity) or bfloat16 (throughput); got {compute_dtype}")
-        self.compute_dtype = compute_dtype
-        self.workspace_cap = int(workspace_cap)
+        super().__init__(compute_dtype, workspace_cap)
         w1, b1 = folded_conv1(weights[CONV1_KEY + ".weight"], weights[CONV1_KEY + ".bias"], weights["scaling_layer.shift"], weights["scaling_layer.scale"])
         self.register_buffer("w0", w1.t().contiguous().float(), persistent=False)        # [9][64], tap-major
         self.register_buffer("b0", b1.float(), persistent=False)
@@ -145,7 +105,6 @@ class LpipsSqueeze(torch.nn.Module):
             self.register_buffer(f"eb{i}", bm, persistent=False)
         for i, key in enumerate(LIN_KEYS):
             self.register_buffer(f"lin{i}", weights[key].float().reshape(-1).clone(), persistent=False)
-        self._ops = {}
 
     def _fire(self, i: int) -> Tuple[Conv2dOp, Conv2dOp]:
         """(squeeze, merged expand) operators of Fire module i on the buffers' device"""
@@ -159,87 +118,53 @@ class LpipsSqueeze(torch.nn.Module):
 
     @staticmethod
     def bytes_per_slice(h: int, w: int, esize: int) -> int:
-        """activations of both images + gradients of one, per kept slice (the chunk size follows from the workspace cap)"""
         (h1, h2, h3, h4), (w1, w2, w3, w4) = extents(h), extents(w)
         act = h1 * w1 * 64 + h2 * w2 * (64 + 2 * (16 + 128)) + h3 * w3 * (128 + 2 * (32 + 256)) + h4 * w4 * (256 + 2 * (48 + 384) + 2 * (64 + 512))
         return 3 * act * esize + 2 * (h2 * w2 * 64 + h3 * w3 * 128 + h4 * w4 * 256)
 
-    def view_term(self, y: torch.Tensor, y_pred: torch.Tensor, view: int, ids: torch.Tensor, grad: Optional[torch.Tensor], scale: float,
-                  normalize: bool, chunk: Optional[int] = None) -> torch.Tensor:
-        """d [S] fp32 = LPIPS(y slice, y_pred slice) for the kept slices ``ids`` (device int32) of ``view``; when ``grad`` (fp32 volume) is given,
-        grad += scale * d sum(d) / d y_pred.  Launches per chunk: 2 first layers (one per image), 3 pools, 16 GEMM forwards, 7 heads; with a gradient
-        16 data-gradient GEMMs, 3 pool backwards and 1 first-layer adjoint."""
-        lib, st = _ffi.lib(), _ffi.stream()
+    def _features(self, y, y_pred, view, cid, normalize):
+        """Launches: 2 first layers (one per image), 3 pools, 16 GEMM forwards.  saved = (the squeeze outputs, the module outputs, the pools' argmax maps by
+        the index of the module behind each pool)."""
         B, _, D, H, W = y.shape
-        h, w = ((H, W), (D, W), (D, H))[view]
-        dt, did = self.compute_dtype, _ffi.dtype_id(self.compute_dtype)
-        S_all = ids.numel()
-        d = torch.zeros(S_all, dtype=torch.float32, device=y.device)
-        if chunk is None:
-            chunk = max(1, self.workspace_cap // self.bytes_per_slice(h, w, 2 if dt == torch.bfloat16 else 4))
-        h1, w1 = extents(h)[0], extents(w)[0]
+        S, dt = cid.numel(), self.compute_dtype
+        h, w = slice_sides(y.shape, view)
         fires = [self._fire(i) for i in range(len(FIRES))]
-        lins = [getattr(self, f"lin{i}") for i in range(7)]
+        t1 = torch.empty((2 * S, extents(h)[0], extents(w)[0], 64), dtype=dt, device=y.device)
+        for half, vol in enumerate((y, y_pred)):
+            _ffi.check(_ffi.lib().sa_lpips_squeeze_conv1_fwd(_ffi.ptr(vol), _ffi.dtype_id(dt), _ffi.ptr(self.w0), _ffi.ptr(self.b0),
+                                                             ctypes.c_void_p(t1[half * S:].data_ptr()), _ffi.ptr(cid), S, view, B, D, H, W, int(normalize),
+                                                             _ffi.stream()), "sa_lpips_squeeze_conv1_fwd")
+        taps, zs, outs, idxs = [t1], [], [], {}
+        x = t1
+        for i, (feat, *_rest) in enumerate(FIRES):
+            if feat in (3, 6, 9):                          # features 2, 5, 8: the ceil-mode pools in front of these modules
+                x, idxs[i] = self._pool(x, ceil=True)
+            z = fires[i][0].fprop(x)
+            x = fires[i][1].fprop(z)
+            zs.append(z)
+            outs.append(x)
+            if i in TAP_FIRES:
+                taps.append(x)
+        return taps, (zs, outs, idxs)
 
-        def pool(x):
-            N, hi, wi, C = x.shape
-            p = torch.empty((N, ceil_pool_extent(hi), ceil_pool_extent(wi), C), dtype=dt, device=x.device)
-            idx = torch.empty(p.shape, dtype=torch.uint8, device=x.device)
-            _ffi.check(lib.sa_lpips_maxpool_ceil_fwd(_ffi.ptr(x), did, _ffi.ptr(p), _ffi.ptr(idx), N, hi, wi, C, st), "sa_lpips_maxpool_ceil_fwd")
-            return p, idx
-
-        def unpool(gp, idx, addend, mask, shape):
-            """gradient at a pool's input [S, hi, wi, C] (prediction half) from the gradient at its output"""
-            _, hi, wi, C = shape
-            gx = torch.empty((gp.shape[0], hi, wi, C), dtype=dt, device=gp.device)
-            _ffi.check(lib.sa_lpips_maxpool_ceil_bwd(_ffi.ptr(gp), ctypes.c_void_p(idx.data_ptr()), _ffi.ptr(addend),
-                                                     ctypes.c_void_p(mask.data_ptr()) if mask is not None else None, did, _ffi.ptr(gx), gp.shape[0], hi, wi, C, st),
-                       "sa_lpips_maxpool_ceil_bwd")
-            return gx
-
-        for lo in range(0, S_all, chunk):
-            cid = ids[lo:lo + chunk]
-            S = cid.numel()
-            t1 = torch.empty((2 * S, h1, w1, 64), dtype=dt, device=y.device)
-            for half, vol in enumerate((y, y_pred)):
-                _ffi.check(lib.sa_lpips_squeeze_conv1_fwd(_ffi.ptr(vol), did, _ffi.ptr(self.w0), _ffi.ptr(self.b0), ctypes.c_void_p(t1[half * S:].data_ptr()),
-                                                          _ffi.ptr(cid), S, view, B, D, H, W, int(normalize), st), "sa_lpips_squeeze_conv1_fwd")
-            taps, zs, outs, idxs = [t1], [], [], {}
-            x = t1
-            for i, (feat, *_rest) in enumerate(FIRES):
-                if feat in (3, 6, 9):                          # features 2, 5, 8: the ceil-mode pools in front of these modules
-                    x, idxs[i] = pool(x)
-                z = fires[i][0].fprop(x)
-                x = fires[i][1].fprop(z)
-                zs.append(z)
-                outs.append(x)
-                if i in TAP_FIRES:
-                    taps.append(x)
-            dc = d[lo:lo + S]
-            gh = []
-            for l in range(7):
-                _, hl, wl, C = taps[l].shape
-                g1 = torch.empty((S, hl, wl, C), dtype=dt, device=y.device) if grad is not None else None
-                _ffi.check(lib.sa_lpips_head(_ffi.ptr(taps[l]), ctypes.c_void_p(taps[l][S:].data_ptr()), did, _ffi.ptr(lins[l]), S, hl * wl, C, _ffi.ptr(dc),
-                                             _ffi.ptr(g1), int(l == 6), st), "sa_lpips_head")
-                gh.append(g1)
-            if grad is None:
-                continue
-            # data gradients of the prediction's half, module by module from the last: g is the gradient at the PRE-activation output of module i's merged
-            # expand.  Its data gradient takes the squeeze's ReLU output as mask; the squeeze's data gradient then adds the head's own gradient at the tap in
-            # front of it (if that input is a tap) and takes that input as mask; where a pool lies in front, the pool backward takes addend and mask instead.
-            # The first tap's ReLU mask is applied by the first layer's adjoint.
-            head_of = {fi: l for l, fi in enumerate(TAP_FIRES) if fi is not None}        # Fire index -> tap index of its output
-            g = gh[6]
-            for i in range(len(FIRES) - 1, -1, -1):
-                g = fires[i][1].dgrad(g, mask=zs[i][S:])
-                src = outs[i - 1] if i else t1                 # what feeds module i, through a pool where one lies in front: [2 S, ...]
-                l_src = head_of.get(i - 1) if i else 0
-                add = gh[l_src] if l_src is not None else None
-                if i in idxs:
-                    g = unpool(fires[i][0].dgrad(g), idxs[i][S:], add, src[S:] if i else None, src.shape)
-                else:
-                    g = fires[i][0].dgrad(g, addend=add, mask=src[S:])
-            _ffi.check(lib.sa_lpips_squeeze_conv1_bwd(_ffi.ptr(g), ctypes.c_void_p(t1[S:].data_ptr()), did, _ffi.ptr(self.w0), _ffi.ptr(grad), _ffi.ptr(cid), S, view,
-                                                      B, D, H, W, float(scale) * (2.0 if normalize else 1.0), st), "sa_lpips_squeeze_conv1_bwd")
-        return d
+    def _input_grad(self, gh, taps, saved, grad, view, cid, scale):
+        """Launches: 16 data-gradient GEMMs, 3 pool backwards, 1 first-layer adjoint.  Data gradients of the prediction's half, module by module from the
+        last: g is the gradient at the PRE-activation output of module i's merged expand.  Its data gradient takes the squeeze's ReLU output as mask; the
+        squeeze's data gradient then adds the head's own gradient at the tap in front of it (if that input is a tap) and takes that input as mask; where a
+        pool lies in front, the pool backward takes addend and mask instead.  The first tap's ReLU mask is applied by the first layer's adjoint."""
+        B, _, D, H, W = grad.shape
+        S, t1, (zs, outs, idxs) = cid.numel(), taps[0], saved
+        fires = [self._fire(i) for i in range(len(FIRES))]
+        head_of = {fi: l for l, fi in enumerate(TAP_FIRES) if fi is not None}        # Fire index -> tap index of its output
+        g = gh[6]
+        for i in range(len(FIRES) - 1, -1, -1):
+            g = fires[i][1].dgrad(g, mask=zs[i][S:])
+            src = outs[i - 1] if i else t1                 # what feeds module i, through a pool where one lies in front: [2 S, ...]
+            l_src = head_of.get(i - 1) if i else 0
+            add = gh[l_src] if l_src is not None else None
+            if i in idxs:
+                g = self._unpool(fires[i][0].dgrad(g), idxs[i][S:], add, src[S:] if i else None, src.shape, ceil=True)
+            else:
+                g = fires[i][0].dgrad(g, addend=add, mask=src[S:])
+        _ffi.check(_ffi.lib().sa_lpips_squeeze_conv1_bwd(_ffi.ptr(g), ctypes.c_void_p(t1[S:].data_ptr()), _ffi.dtype_id(self.compute_dtype), _ffi.ptr(self.w0),
+                                                         _ffi.ptr(grad), _ffi.ptr(cid), S, view, B, D, H, W, scale, _ffi.stream()), "sa_lpips_squeeze_conv1_bwd")

@@ -392,7 +392,42 @@ def _lpips_network(name: str, net: str, weights: Dict, compute_dtype: torch.dtyp
 _FAKE_3D_VIEW = {2: 0, 3: 1, 4: 2}      # fake_3d_axis entry -> view id of sa_lpips_unfold (the reference's permutes (0,2,1,3,4), (0,3,1,2,4), (0,4,1,2,3))
 
 
-class _PerceptualLoss(torch.nn.Module):
+class _SliceLpipsLoss(torch.nn.Module):
+    """What the losses with a 2.5D LPIPS term share: the step that keys the slice draw, the refusals every such loss makes of its volumes, the per-view
+    draw and the commitment-cost tail.  Subclasses set ``seed``, ``step`` and ``summaries``."""
+
+    def set_step(self, step: int) -> int:
+        """the global training iteration: with the seed and the view it keys the slice draw, so a resumed run reproduces it"""
+        self.step = int(step)
+        return self.step
+
+    def _check_volumes(self, y_pred: torch.Tensor, y: torch.Tensor):
+        name = type(self).__name__
+        if y_pred.dim() != 5:
+            raise ValueError(f"{name} needs [B, 1, D, H, W] volumes; got {tuple(y_pred.shape)}")
+        if tuple(y.shape) != tuple(y_pred.shape):
+            raise ValueError(f"{name}: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
+        if y_pred.shape[1] != 1:
+            raise NotImplementedError(f"{name}: C = 1 only (the single channel broadcasts to LPIPS' three); got C={y_pred.shape[1]}")
+
+    def _draw_ids(self, y_pred: torch.Tensor, views, n_keep) -> List[torch.Tensor]:
+        """per view the kept slice ids (``n_keep(n)`` of its n = B * extent slices) on the prediction's device: small int32 uploads"""
+        from . import lpips
+        B, _, D, H, W = y_pred.shape
+        return [torch.from_numpy(lpips.draw_slices(self.seed, self.step, v, B * (D, H, W)[v], n_keep(B * (D, H, W)[v]))).to(y_pred.device) for v in views]
+
+    def _add_commitment(self, loss: torch.Tensor, network_output) -> torch.Tensor:
+        for idx, ql in enumerate(network_output["quantization_losses"]):
+            ql = ql.float()
+            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
+            loss = loss + ql
+        return loss
+
+    def get_summaries(self):
+        return self.summaries
+
+
+class _PerceptualLoss(_SliceLpipsLoss):
     """What ``PerceptualLoss``, ``JukeboxPerceptualLoss`` and ``HartleyPerceptualLoss`` share: the 2.5D LPIPS term -- alex by default (losses/lpips.py,
     csrc/lpips.hip), squeeze with ``lpips_kwargs={"net": "squeeze"}`` (losses/lpips_squeeze.py; section 7.13) --, the pixel term and
     the commitment terms.  Beyond upstream's constructor arguments: ``perceptual_weights`` (a validated state dict in the layout of that network,
@@ -434,22 +469,12 @@ class _PerceptualLoss(torch.nn.Module):
         self.chunk_slices = None           # None: from the workspace cap (tests halve it)
         self.summaries: Dict = {"scalar": {}}
 
-    def set_step(self, step: int) -> int:
-        """the global training iteration: with the seed and the view it keys the slice draw, so a resumed run reproduces it"""
-        self.step = int(step)
-        return self.step
-
     def _n_keep(self, n_slices: int) -> int:
         return int(n_slices * self.keep_ratio)
 
     def _check(self, y_pred: torch.Tensor, y: torch.Tensor):
         name = type(self).__name__
-        if y_pred.dim() != 5:
-            raise ValueError(f"{name} needs [B, 1, D, H, W] volumes; got {tuple(y_pred.shape)}")
-        if tuple(y.shape) != tuple(y_pred.shape):
-            raise ValueError(f"{name}: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
-        if y_pred.shape[1] != 1:
-            raise NotImplementedError(f"{name}: C = 1 only (the single channel broadcasts to LPIPS' three); got C={y_pred.shape[1]}")
+        self._check_volumes(y_pred, y)
         B, _, D, H, W = y_pred.shape
         for v in self.fake_3D_views:
             n, sides = ((D, (H, W)), (H, (D, W)), (W, (D, H)))[v]
@@ -462,12 +487,8 @@ class _PerceptualLoss(torch.nn.Module):
     def _perceptual(self, y_pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """the sum of the per-view terms (differentiable to y_pred), summaries written"""
         from . import lpips
-        self._check(y_pred, y)
-        B, _, D, H, W = y_pred.shape
-        ids = []
-        for v in self.fake_3D_views:          # every refusal above comes before the first launch; the lists are small int32 uploads
-            n = B * (D, H, W)[v]
-            ids.append(torch.from_numpy(lpips.draw_slices(self.seed, self.step, v, n, self._n_keep(n))).to(y_pred.device))
+        self._check(y_pred, y)          # every refusal comes before the first launch
+        ids = self._draw_ids(y_pred, self.fake_3D_views, self._n_keep)
         total, *terms = lpips.PerceptualFn.apply(y_pred, y, self.perceptual_function, tuple(self.fake_3D_views), ids, float(self.perceptual_factor),
                                                  self.lpips_normalize, self.chunk_slices)
         for idx, t in enumerate(terms):
@@ -480,11 +501,7 @@ class _PerceptualLoss(torch.nn.Module):
             l2 = hip_mse(y_pred, y)
             self.summaries["scalar"]["Loss-MSE-Reconstruction"] = l2.detach()
             loss = loss + l2
-        for idx, ql in enumerate(network_output["quantization_losses"]):
-            ql = ql.float()
-            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
-            loss = loss + ql
-        return loss
+        return self._add_commitment(loss, network_output)
 
     def _spectral(self, y_pred, y):
         return None
@@ -496,9 +513,6 @@ class _PerceptualLoss(torch.nn.Module):
         spec = self._spectral(y_pred, y)
         p = self._perceptual(y_pred, y)
         return self._tail(p if spec is None else spec + p, y_pred, y, network_output)
-
-    def get_summaries(self):
-        return self.summaries
 
     def get_perceptual_factor(self) -> float:
         return self.perceptual_factor
@@ -576,16 +590,10 @@ class _BaselinePerceptualFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, net, ids, factor: float, chunk):
-        _ffi.require_gpu()
-        a = pred.contiguous()
-        b = target.contiguous().to(a.device)
-        grad = torch.zeros_like(a) if pred.requires_grad else None
-        means = []
-        for view, vid in zip(_BaselinePerceptualFn.VIEWS, ids):
-            d = net.view_term(b, a, view, vid, grad, factor / vid.numel(), False, chunk)     # (upstream calls LPIPS without normalize)
-            means.append(d.double().sum().div(vid.numel()).float())
+        from . import lpips
+        ctx.grad, sums = lpips.view_sums(pred, target, net, _BaselinePerceptualFn.VIEWS, ids, factor, False, chunk)      # (upstream calls LPIPS without normalize)
+        means = [s.div(vid.numel()).float() for s, vid in zip(sums, ids)]
         total = ((means[0] + means[1]) + means[2]) * factor
-        ctx.grad = grad
         ctx.mark_non_differentiable(*means)
         return (total, *means)
 
@@ -596,7 +604,7 @@ class _BaselinePerceptualFn(torch.autograd.Function):
         return (grad * g if grad is not None else None), None, None, None, None, None
 
 
-class BaselineLoss(torch.nn.Module):
+class BaselineLoss(_SliceLpipsLoss):
     """``BaselineLoss()`` of the reference (src/losses/vqvae/vqvae.py:1648-1780, ``--loss=baseline``): ``pixel_factor * l1(pred, y) + fft_factor *
     mse(|fftn((y + 1) / 2)|, |fftn((pred + 1) / 2)|) + perceptual_factor * (three-plane mean LPIPS-squeeze) + sum(quantization_losses)``.
 
@@ -624,18 +632,8 @@ class BaselineLoss(torch.nn.Module):
         self.chunk_slices = None           # None: from the workspace cap (tests set it)
         self.summaries: Dict = {"scalar": {}}
 
-    def set_step(self, step: int) -> int:
-        """the global training iteration: with the seed and the view it keys the slice draw, so a resumed run reproduces it"""
-        self.step = int(step)
-        return self.step
-
     def _check(self, y_pred: torch.Tensor, y: torch.Tensor):
-        if y_pred.dim() != 5:
-            raise ValueError(f"BaselineLoss needs [B, 1, D, H, W] volumes; got {tuple(y_pred.shape)}")
-        if tuple(y.shape) != tuple(y_pred.shape):
-            raise ValueError(f"BaselineLoss: target shape {tuple(y.shape)} differs from the reconstruction's {tuple(y_pred.shape)}")
-        if y_pred.shape[1] != 1:
-            raise NotImplementedError(f"BaselineLoss: C = 1 only (the single channel broadcasts to LPIPS' three); got C={y_pred.shape[1]}")
+        self._check_volumes(y_pred, y)
         if min(y_pred.shape[2:]) < self._min_side:
             raise ValueError(f"BaselineLoss: every slice side must be >= {self._min_side} (the smallest for which SqueezeNet's third ceil-mode pool still has "
                              f"an output); got a volume of {' x '.join(map(str, y_pred.shape[2:]))}")
@@ -661,12 +659,7 @@ class BaselineLoss(torch.nn.Module):
         return loss
 
     def _calculate_perceptual_loss(self, y_pred, y):
-        from . import lpips
-        B, _, D, H, W = y_pred.shape
-        ids = []
-        for v in _BaselinePerceptualFn.VIEWS:         # small int32 uploads; every refusal comes before the first launch
-            n = B * (D, H, W)[v]
-            ids.append(torch.from_numpy(lpips.draw_slices(self.seed, self.step, v, n, min(int(self.n_slices), n))).to(y_pred.device))
+        ids = self._draw_ids(y_pred, _BaselinePerceptualFn.VIEWS, lambda n: min(int(self.n_slices), n))     # (forward's refusals come first)
         loss, sag, axi, cor = _BaselinePerceptualFn.apply(y_pred, y, self.perceptual_function, ids, float(self.perceptual_factor), self.chunk_slices)
         self.summaries["scalar"]["Loss-Perceptual_Sagittal-Reconstruction"] = sag.detach()
         self.summaries["scalar"]["Loss-Perceptual_Axial-Reconstruction"] = axi.detach()
@@ -680,19 +673,22 @@ class BaselineLoss(torch.nn.Module):
         self._check(y_pred, y)
         y = y.to(y_pred.device)
         loss = self._calculate_pixel_loss(y_pred, y) + self._calculate_frequency_loss(y_pred, y) + self._calculate_perceptual_loss(y_pred, y)
-        for idx, ql in enumerate(network_output["quantization_losses"]):
-            ql = ql.float()
-            self.summaries["scalar"][f"Loss-MSE-VQ{idx}_Commitment_Cost"] = ql.detach()
-            loss = loss + ql
-        return loss
-
-    def get_summaries(self):
-        return self.summaries
+        return self._add_commitment(loss, network_output)
 
 
 # the reference's src/losses/vqvae/utils.py list, complete; the LPIPS family and "baseline" (LPIPS-squeeze) need --perceptual_weights (this build downloads nothing)
 VQVAE_LOSSES = ("baur", "mse", "jukebox", "spectral", "hartley", "wavegan", "perceptual", "jukebox_perceptual", "hartley_perceptual", "baseline")
 _PERCEPTUAL_LOSSES = {"perceptual": PerceptualLoss, "jukebox_perceptual": JukeboxPerceptualLoss, "hartley_perceptual": HartleyPerceptualLoss}
+
+
+def _lpips_arguments(config: dict, net: str) -> dict:
+    """what the configuration gives every loss with an LPIPS term: the validated weights of ``net``, the compute dtype and the seed of the slice draw"""
+    from . import lpips
+    weights = config["perceptual_weights"]
+    if not isinstance(weights, dict):
+        weights = lpips.load_weights(weights, net=net)
+    dtype = config.get("compute_dtype") or (torch.bfloat16 if config.get("amp") else torch.float32)
+    return {"perceptual_weights": weights, "compute_dtype": dtype, "seed": int(config.get("seed") or 0)}
 
 
 def get_vqvae_loss(config: dict) -> torch.nn.Module:
@@ -711,20 +707,9 @@ def get_vqvae_loss(config: dict) -> torch.nn.Module:
         return WaveGANLoss(dimensions=3)
     if config["loss"] in _PERCEPTUAL_LOSSES and config.get("perceptual_weights"):
         # drop_ratio 0.5 as src/losses/vqvae/configure.py:40-45; the weights come from --perceptual_weights (host only, refused by name when wrong)
-        from . import lpips
-        weights = config["perceptual_weights"]
-        if not isinstance(weights, dict):
-            weights = lpips.load_weights(weights)
-        dtype = config.get("compute_dtype") or (torch.bfloat16 if config.get("amp") else torch.float32)
-        return _PERCEPTUAL_LOSSES[config["loss"]](dimensions=3, drop_ratio=0.5, perceptual_weights=weights, compute_dtype=dtype,
-                                                  seed=int(config.get("seed") or 0))
+        return _PERCEPTUAL_LOSSES[config["loss"]](dimensions=3, drop_ratio=0.5, **_lpips_arguments(config, "alex"))
     if config["loss"] == "baseline" and config.get("perceptual_weights"):
         # src/losses/vqvae/configure.py builds BaselineLoss() without arguments; the LPIPS-squeeze weights come from --perceptual_weights
-        from . import lpips
-        weights = config["perceptual_weights"]
-        if not isinstance(weights, dict):
-            weights = lpips.load_weights(weights, net="squeeze")
-        dtype = config.get("compute_dtype") or (torch.bfloat16 if config.get("amp") else torch.float32)
-        return BaselineLoss(perceptual_weights=weights, compute_dtype=dtype, seed=int(config.get("seed") or 0))
+        return BaselineLoss(**_lpips_arguments(config, "squeeze"))
     hint = " The LPIPS family needs --perceptual_weights=<file | random:seed>." if config["loss"] in (*_PERCEPTUAL_LOSSES, "baseline") else ""
     raise ValueError(f"Loss function unknown. Was given {config['loss']} but choices are {list(VQVAE_LOSSES)}.{hint}")

@@ -184,6 +184,8 @@ def test_maxpool_kernels_match_torch_with_ties_and_a_dropped_column():
     yr = F.max_pool2d(x64, 3, 2)
     gy = torch.randn(yr.shape, generator=g).bfloat16().float()
     yr.backward(gy.double())
+    add = torch.randn(S, Hi, Wi, C, generator=g).bfloat16().float()
+    mask = torch.relu(torch.randn(S, Hi, Wi, C, generator=g)).bfloat16().float()
     for dt in (torch.float32, torch.bfloat16):
         did = _ffi.dtype_id(dt)
         xc = x.permute(0, 2, 3, 1).contiguous().to(DEV).to(dt)
@@ -193,12 +195,19 @@ def test_maxpool_kernels_match_torch_with_ties_and_a_dropped_column():
         gx = torch.empty_like(xc)
         gyc = gy.permute(0, 2, 3, 1).contiguous().to(DEV).to(dt)
         _ffi.check(lib.sa_lpips_maxpool_bwd(_ffi.ptr(gyc), _ffi.ptr(idx), None, None, did, _ffi.ptr(gx), S, Hi, Wi, C, _ffi.stream()), "bwd")
+        gm = torch.empty_like(xc)
+        addc, maskc = add.to(DEV).to(dt), mask.to(DEV).to(dt)
+        _ffi.check(lib.sa_lpips_maxpool_bwd(_ffi.ptr(gyc), _ffi.ptr(idx), _ffi.ptr(addc), _ffi.ptr(maskc), did, _ffi.ptr(gm), S, Hi, Wi, C, _ffi.stream()),
+                   "bwd + addend + mask")
         torch.cuda.synchronize()
         assert torch.equal(y.float().cpu().permute(0, 3, 1, 2).double(), yr.detach())
         got = gx.float().cpu().permute(0, 3, 1, 2).double()
         # (a position that is the first maximum of several windows sums their gradients: exact in fp32, one rounding in bf16)
         assert float((got - x64.grad).abs().max()) <= (0 if dt == torch.float32 else 2.0 ** -7 * float(x64.grad.abs().max()))
         assert bool((got[..., 7] == 0).all()), "the column no window covers must get an exactly zero gradient"
+        want = (x64.grad.permute(0, 2, 3, 1) + add.double()) * (mask > 0)
+        assert float((gm.float().cpu().double() - want).abs().max()) <= (1e-6 if dt == torch.float32 else 2.0 ** -7) * float(want.abs().max())
+        assert bool((gm.float().cpu()[mask == 0] == 0).all())
 
 
 @functools.lru_cache(maxsize=None)
