@@ -368,6 +368,18 @@ typedef struct sa_anomaly_params {
 int sa_anomaly_map(const float *x, const float *r, const float *m, const unsigned char *label, float *a_out, const sa_anomaly_params *params,
                    void *results, void *ws, void *stream);
 int64_t sa_anomaly_map_workspace_bytes(const sa_anomaly_params *params);
+/* The ensemble of sa_anomaly_map over `members` healings of the same scans (metrics/anomaly.py: anomaly_map_ensemble, run_vqvae.py --anomaly_ensemble;
+ * DESIGN 7.15), in one pass: member k has the reconstruction r + k * r_member_stride [B, D, H, W] and, when m is not NULL, the weight grid
+ * m + k * m_member_stride [B, d, h, w] (strides in elements, each at least one member's extent); x, label, params, results and ws are as for
+ * sa_anomaly_map (ws: sa_anomaly_map_workspace_bytes(params) bytes) and shared by the members.  With a_k the number sa_anomaly_map computes for
+ * (x, r_k, m_k):  s = a_0;  s = s + a_k in fp32 for k = 1 .. members - 1, in member order;  a = s * inv_K, inv_K = (float)(1.0 / (double)members).
+ * a_out receives a and the summaries are those of a, with the batch invariance and repeatability of sa_anomaly_map; members = 1 gives sa_anomaly_map's
+ * bits.  SA_EINVAL (nothing launched) for members outside 1..SA_ANOMALY_MAX_MEMBERS, a member stride below a member's extent (m's only when m is given)
+ * and whatever sa_anomaly_map refuses that way; SA_EUNSUPPORTED as sa_anomaly_map gives it. */
+#define SA_ANOMALY_MAX_MEMBERS 16
+int sa_anomaly_map_ensemble(const float *x, const float *r, int64_t r_member_stride, const float *m, int64_t m_member_stride,
+                            const unsigned char *label, float *a_out, const sa_anomaly_params *params, int members, void *results, void *ws,
+                            void *stream);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

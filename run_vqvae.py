@@ -53,6 +53,12 @@ edges with its threshold, and the average precision).  ``--anomaly_weight=mask|n
 its upsampling (None: half the down-sampling factor), ``--anomaly_residual=abs|positive|negative`` the sign convention, ``--anomaly_threshold`` the
 operating point of the TP / FP / FN counts, ``--anomaly_hist_max`` the top of the histogram, ``--anomaly_labels`` any input spec of label volumes
 (matched by stem, reoriented and cropped like the scans, never normalised, class 1 where > 0.5).
+
+``--anomaly_ensemble=<dir|glob>,<dir|glob>[,...]`` (MI355X-only; default None: nothing changes) scores every scan against 2 to 16 healings of
+its codes, one ``run_transformer.py --mode=healing`` outputs directory per ordering or seed: every spec is searched like ``--anomaly_codes`` (which it
+replaces; giving both is refused), every member is decoded on its own, and ``sa_anomaly_map_ensemble`` writes the mean of the members' weighted residuals
+as ``<name>_anomaly_map`` in one pass, with the scores of that mean; ``<name>_healed_reconstruction_m<k>`` is member k's decoding in flag order and
+``anomaly_scores_rank<k>.csv`` gains a last column ``members``.  The other ``--anomaly_*`` flags are shared by the members.
 """
 import os
 import sys
@@ -80,6 +86,7 @@ DEFAULTS = dict(
     output_ext=".npy", output_dtype="float32", perceptual_weights=None,
     codebook_restart_patience=None, codebook_restart_max=32,
     anomaly_codes=None, anomaly_weight="mask", anomaly_sigma=None, anomaly_residual="abs", anomaly_threshold=None, anomaly_hist_max=1.0, anomaly_labels=None,
+    anomaly_ensemble=None,
 )
 MODES = ["training", "extracting", "decoding", "anomaly"]
 
@@ -539,9 +546,34 @@ def _anomaly_sigma(cfg):
     return cfg["anomaly_sigma"] if cfg["anomaly_sigma"] is not None else _downsampling_factor(cfg) / 2.0
 
 
+def _ensemble_specs(cfg):
+    """--anomaly_ensemble as a list of specs (a comma-separated string, a tuple or a list), or None without the flag"""
+    v = cfg["anomaly_ensemble"]
+    if v is None:
+        return None
+    return v.split(",") if isinstance(v, str) else list(v) if isinstance(v, (tuple, list)) else [v]
+
+
 def _check_anomaly_flags(cfg):
     """the --anomaly_* flags act or refuse (before anything touches the device)"""
-    from synthanatomy_amd.metrics.anomaly import MAX_SIGMA, RESIDUALS
+    from synthanatomy_amd.metrics.anomaly import MAX_MEMBERS, MAX_SIGMA, RESIDUALS
+    specs = _ensemble_specs(cfg)
+    if specs is not None:
+        flag = f"--anomaly_ensemble={cfg['anomaly_ensemble']}"
+        if cfg["mode"] != "anomaly":
+            raise ValueError(f"{flag}: the flag belongs to --mode=anomaly, not --mode={cfg['mode']}")
+        for sp in specs:
+            if not isinstance(sp, str):
+                raise ValueError(f"{flag}: {sp!r} is not a directory or a glob (a comma-separated string or a tuple of strings is needed)")
+            if not sp.strip():
+                raise ValueError(f"{flag}: an empty spec (one directory or glob per member is needed)")
+        if not 2 <= len(specs) <= MAX_MEMBERS:
+            raise ValueError(f"{flag}: {len(specs)} members, 2 to {MAX_MEMBERS} are needed (one healing: --anomaly_codes)")
+        twice = sorted({sp for sp in specs if specs.count(sp) > 1})
+        if twice:
+            raise ValueError(f"{flag}: {twice[0]} is given twice (every member needs its own healing outputs)")
+        if cfg["anomaly_codes"] is not None:
+            raise ValueError(f"{flag} with --anomaly_codes={cfg['anomaly_codes']}: the ensemble names every member's outputs itself; give one of the two")
     if cfg["anomaly_weight"] not in ("mask", "nll", "none"):
         raise ValueError(f"--anomaly_weight={cfg['anomaly_weight']}: choices are mask, nll and none")
     if cfg["anomaly_residual"] not in RESIDUALS:
@@ -590,6 +622,26 @@ def find_healing_outputs(subjects, spec, weight="mask"):
     return out
 
 
+def find_ensemble_outputs(subjects, specs, weight="mask"):
+    """``find_healing_outputs`` once per member spec: a list over the members of lists over the subjects.  A subject whose two members resolve to the
+    same healed file, and a member whose code grid differs in shape from member 0's, are refused by name (host only: the ``.npy`` headers are read)."""
+    members = [find_healing_outputs(subjects, spec, weight) for spec in specs]
+    for j, s in enumerate(subjects):
+        seen = {}
+        for k, recs in enumerate(members):
+            real = os.path.realpath(recs[j]["healed"])
+            if real in seen:
+                raise ValueError(f"{s}: members {seen[real]} ({specs[seen[real]]}) and {k} ({specs[k]}) of --anomaly_ensemble resolve to the same "
+                                 f"healed file {recs[j]['healed']}")
+            seen[real] = k
+        shapes = [np.load(recs[j]["healed"], mmap_mode="r").shape for recs in members]
+        for k, shp in enumerate(shapes):
+            if shp != shapes[0]:
+                raise ValueError(f"{s}: member {k} ({specs[k]}) of --anomaly_ensemble has a code grid of shape {shp}, member 0 ({specs[0]}) has "
+                                 f"{shapes[0]}")
+    return members
+
+
 def match_labels(subjects, spec):
     """the label volume of every subject, matched by stem among ``list_inputs(spec)``; a subject without exactly one is refused by name"""
     found = list_inputs(spec)
@@ -605,9 +657,13 @@ def match_labels(subjects, spec):
 def anomaly(cfg, rank, local, world, dev):
     """--mode=anomaly: every validation subject against the decoding of its healed codes, on the device from the scan to the scores."""
     import csv
-    from synthanatomy_amd.metrics.anomaly import anomaly_map, average_precision, best_dice, dice_from_counts
+    from synthanatomy_amd.metrics.anomaly import anomaly_map, anomaly_map_ensemble, average_precision, best_dice, dice_from_counts
     files = list_inputs(cfg["validation_subjects"])
-    healed = find_healing_outputs(files, cfg["anomaly_codes"] or cfg["outputs_directory"], cfg["anomaly_weight"])      # host only: refusals come first
+    specs = _ensemble_specs(cfg)      # DESIGN 7.15: K healings per subject, one fused map; None: the single healing of 7.11
+    if specs is None:
+        members = [find_healing_outputs(files, cfg["anomaly_codes"] or cfg["outputs_directory"], cfg["anomaly_weight"])]      # host only: refusals come first
+    else:
+        members = find_ensemble_outputs(files, specs, cfg["anomaly_weight"])
     label_files = match_labels(files, cfg["anomaly_labels"]) if cfg["anomaly_labels"] is not None else None
     sigma = _anomaly_sigma(cfg)
     net = build_network(cfg, dev).eval()
@@ -628,36 +684,54 @@ def anomaly(cfg, rank, local, world, dev):
     try:
         with torch.no_grad():
             for names, x, headers in _batches(files, order, cfg["eval_batch_size"], cfg, gen, dev):
-                grids, weights = [], []
-                for n in names:
-                    h = healed[index[n]]
-                    codes = np.load(h["healed"]).astype(np.int64)
-                    if codes.min() < 0 or codes.max() >= net.n_embed:      # the check of --mode=decoding
-                        raise ValueError(f"{h['healed']}: code {int(codes.max())} is not a codebook entry (num_embeddings={net.n_embed})")
-                    grids.append(torch.from_numpy(codes))
-                    if cfg["anomaly_weight"] != "none":
-                        wgt = np.load(h["resampled" if cfg["anomaly_weight"] == "mask" else "nll"]).astype(np.float32)
-                        if wgt.shape != codes.shape:
-                            raise ValueError(f"{n}: the weight grid {wgt.shape} and the healed codes {codes.shape} differ in shape")
-                        weights.append(torch.from_numpy(wgt))
-                rec = net.decode_samples([torch.stack(grids).to(dev)]).float()
-                if rec.shape != x.shape:
-                    raise ValueError(f"{names[0]}: the healed codes decode to {tuple(rec.shape[2:])}, the scan is {tuple(x.shape[2:])} (--roi?)")
+                recs, wgts = [], []      # per member: the decoding [B, 1, D, H, W] and the weight grids [B, d, h, w]
+                for healed in members:      # member by member: each decode_samples call is the one a single-healing run makes for this batch
+                    grids, weights = [], []
+                    for n in names:
+                        h = healed[index[n]]
+                        codes = np.load(h["healed"]).astype(np.int64)
+                        if codes.min() < 0 or codes.max() >= net.n_embed:      # the check of --mode=decoding
+                            raise ValueError(f"{h['healed']}: code {int(codes.max())} is not a codebook entry (num_embeddings={net.n_embed})")
+                        grids.append(torch.from_numpy(codes))
+                        if cfg["anomaly_weight"] != "none":
+                            wgt = np.load(h["resampled" if cfg["anomaly_weight"] == "mask" else "nll"]).astype(np.float32)
+                            if wgt.shape != codes.shape:
+                                raise ValueError(f"{n}: the weight grid {wgt.shape} and the healed codes {codes.shape} differ in shape")
+                            weights.append(torch.from_numpy(wgt))
+                    rec = net.decode_samples([torch.stack(grids).to(dev)]).float()
+                    if rec.shape != x.shape:
+                        raise ValueError(f"{names[0]}: the healed codes decode to {tuple(rec.shape[2:])}, the scan is {tuple(x.shape[2:])} (--roi?)")
+                    if specs is not None:
+                        if not recs:
+                            block = torch.empty((len(members),) + tuple(x.shape), dtype=torch.float32, device=dev)
+                        block[len(recs)].copy_(rec)
+                        rec = block[len(recs)]
+                    recs.append(rec)
+                    wgts.append(torch.stack(weights).to(dev) if weights else None)
                 labels = None
                 if label_files is not None:
                     labels = torch.stack([_load_volume(label_files[index[n]], raw_cfg, gen, dev).reshape(x.shape[1:]) for n in names])
-                amap, summ = anomaly_map(x, rec, torch.stack(weights).to(dev) if weights else None, sigma=sigma, residual=cfg["anomaly_residual"],
-                                         labels=labels, threshold=cfg["anomaly_threshold"], hist_max=cfg["anomaly_hist_max"])
+                if specs is None:
+                    amap, summ = anomaly_map(x, recs[0], wgts[0], sigma=sigma, residual=cfg["anomaly_residual"],
+                                             labels=labels, threshold=cfg["anomaly_threshold"], hist_max=cfg["anomaly_hist_max"])
+                else:
+                    amap, summ = anomaly_map_ensemble(x, block, torch.stack(wgts) if wgts[0] is not None else None, sigma=sigma,
+                                                      residual=cfg["anomaly_residual"], labels=labels, threshold=cfg["anomaly_threshold"],
+                                                      hist_max=cfg["anomaly_hist_max"])
+                posts = ["healed_reconstruction"] if specs is None else [f"healed_reconstruction_m{k}" for k in range(len(members))]
                 if saver is None:
-                    for n, a_, r_ in zip(names, amap.cpu().numpy(), rec.cpu().numpy()):
+                    host = [rec.cpu().numpy() for rec in recs]
+                    for j, (n, a_) in enumerate(zip(names, amap.cpu().numpy())):
                         save_npy(a_[0], cfg["outputs_directory"], n, "anomaly_map", np.float32)
-                        save_npy(r_[0], cfg["outputs_directory"], n, "healed_reconstruction", np.float32)
+                        for post, r_ in zip(posts, host):
+                            save_npy(r_[j, 0], cfg["outputs_directory"], n, post, np.float32)
                 else:
                     saver.batch()
-                    for n, a_, r_, h in zip(names, amap, rec, headers):
+                    for j, (n, a_, h) in enumerate(zip(names, amap, headers)):
                         geom = nifti_output_geometry(h, cfg["roi"], canonical, a_.shape[-3:])
                         saver.save(a_[0], _output_path(cfg, n, "anomaly_map"), *geom)
-                        saver.save(r_[0], _output_path(cfg, n, "healed_reconstruction"), *geom)
+                        for post, rec in zip(posts, recs):
+                            saver.save(rec[j, 0], _output_path(cfg, n, post), *geom)
                 sums, maxs, hist = summ["sum"].cpu().numpy(), summ["max"].cpu().numpy(), summ["hist"].cpu().numpy()
                 counts = [summ[k].cpu().numpy() for k in ("tp", "fp", "fn")] if summ["tp"] is not None else None
                 for j, n in enumerate(names):
@@ -666,11 +740,14 @@ def anomaly(cfg, rank, local, world, dev):
                         bd, bt = best_dice(hist[j, 0], hist[j, 1], summ["inv_bin"])
                         row.update(dice="" if counts is None else repr(dice_from_counts(counts[0][j], counts[1][j], counts[2][j])),
                                    best_dice=repr(bd), best_dice_threshold=repr(bt), average_precision=repr(average_precision(hist[j, 0], hist[j, 1])))
+                    if specs is not None:
+                        row["members"] = str(summ["members"])
                     rows.append(row)
     finally:
         if saver is not None:
             saver.close()
     fields = ["subject", "sum", "max"] + (["dice", "best_dice", "best_dice_threshold", "average_precision"] if label_files is not None else [])
+    fields += ["members"] if specs is not None else []
     with open(os.path.join(cfg["outputs_directory"], f"anomaly_scores_rank{rank}.csv"), "w", newline="") as f:
         wr = csv.DictWriter(f, fieldnames=fields)
         wr.writeheader()
@@ -685,7 +762,7 @@ def run(argv):
         raise ValueError(f"VQVAE mode unknown. Was given {cfg['mode']} but choices are {MODES}.")
     _check_output_flags(cfg)
     _check_codebook_flags(cfg)
-    if cfg["mode"] == "anomaly":
+    if cfg["mode"] == "anomaly" or cfg["anomaly_ensemble"] is not None:
         _check_anomaly_flags(cfg)
     cfg["perceptual_state"] = _check_perceptual_flags(cfg) if cfg["mode"] == "training" else None
     rank, local, world = init_distributed()

@@ -74,6 +74,7 @@ class EgressParams(Structure):
 # include/synthanatomy_hip.h: SA_ANOMALY_MAX_R, SA_ANOMALY_RESULT_WORDS.  One result record per volume, 64-bit words: [0] sum a (double), [1] max a (double
 # holding the float), [2], [3], [4] TP, FP, FN, [5..7] 0, [8 + 256 c + k] voxels of label class c in histogram bin k
 ANOMALY_MAX_R, ANOMALY_RESULT_WORDS = 24, 520
+ANOMALY_MAX_MEMBERS = 16      # SA_ANOMALY_MAX_MEMBERS: members of one sa_anomaly_map_ensemble call
 
 
 class AnomalyParams(Structure):
@@ -139,6 +140,8 @@ _SIGS = {
     "sa_volume_egress_workspace_bytes": (c_int64, []),
     "sa_anomaly_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AnomalyParams), c_void_p, c_void_p, c_void_p]),
     "sa_anomaly_map_workspace_bytes": (c_int64, [POINTER(AnomalyParams)]),
+    "sa_anomaly_map_ensemble": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(AnomalyParams), c_int, c_void_p,
+                                        c_void_p, c_void_p]),
     "sa_bn_sums_ws_floats": (c_int64, [c_int]),
     "sa_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "sa_embed_sum": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p]),

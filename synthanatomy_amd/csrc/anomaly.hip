@@ -19,6 +19,11 @@
 // most of a masked map is zero; TP / FP / FN) go that way too, counted in registers: thousands of blocks adding to ONE address serialise in L2 (measured:
 // 420 us instead of 75 for a 160 x 224 x 160 volume).  The other bins are LDS atomics per block, then 64-bit global atomic adds of the bins that are not
 // empty, 512 contiguous bytes per wave instruction.
+//
+// Ensembles: sa_anomaly_map_ensemble is the same body with a loop over K members (r_k, m_k) inside the block.  x, the label bytes, the taps,
+// the three band tables, the histogram clear and the summary epilogue happen once; per member the thread's 16 r_k values (requested before that
+// member's plane walk and used after it, as the single map's are), the walk over m_k's latent planes through the same ms / T1 buffers, and s = s + e_k w_k in member order
+// (s = a_0 for the first).  The map is a = s inv_K, one fp32 multiply; the summaries are taken over a.  K and every loop bound are uniform over the block.
 #include "sa_common.h"
 
 namespace sa {
@@ -76,10 +81,18 @@ __device__ __forceinline__ float an_band(const float* gs, int R, int p, int c, i
     return s;
 }
 
-__global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ m,
-                                                                 const unsigned char* __restrict__ label, float* __restrict__ a_out, const AnGeom g,
-                                                                 const AnTaps taps, unsigned long long* __restrict__ part,
-                                                                 unsigned long long* __restrict__ results) {
+// members of an ensemble: member k's r and m start k * r_stride and k * m_stride elements after the first one's; inv_K = (float)(1.0 / K) from the host
+struct AnMembers {
+    int K;
+    float inv_K;
+    int64_t r_stride, m_stride;
+};
+
+// ENS = false: one (r, m), the code of sa_anomaly_map (M is not read); ENS = true: the loop over M.K members
+template <bool ENS>
+__device__ __forceinline__ void anomaly_map_body(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ m,
+                                                 const unsigned char* __restrict__ label, float* __restrict__ a_out, const AnGeom& g, const AnTaps& taps,
+                                                 unsigned long long* __restrict__ part, unsigned long long* __restrict__ results, const AnMembers& M) {
     extern __shared__ __attribute__((aligned(16))) char an_smem[];
     float* gs = reinterpret_cast<float*>(an_smem);
     float* AD = gs + 64;
@@ -123,6 +136,24 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __
     float wacc[AN_LD];
 #pragma unroll
     for (int k = 0; k < AN_LD; ++k) wacc[k] = 0.f;
+    // ensembles only: the running sum s, the loads of member km's r (in flight under its own walk, as the first member's are) and the step that closes it
+    [[maybe_unused]] float sacc[AN_LD] = {};
+    [[maybe_unused]] auto load_member = [&](int km) {      // (one pointer stepped from plane to plane: 16 addresses kept across the member loop cost 32 VGPRs)
+        if (km == 0) return;                               // (the first member's came with x)
+        const float* p = r + (km * M.r_stride + base);
+#pragma unroll
+        for (int k = 0; k < AN_LD; ++k, p += plane) rv[k] = (valid && k < np) ? *p : 0.f;
+    };
+    [[maybe_unused]] auto fold = [&](int km) {      // s = a_0, then s = s + a_k with a_k the number sa_anomaly_map computes for member k
+#pragma unroll
+        for (int k = 0; k < AN_LD; ++k) {
+            const float dlt = xv[k] - rv[k];
+            const float e = g.mode == SA_ANOMALY_ABS ? fabsf(dlt) : g.mode == SA_ANOMALY_POSITIVE ? fmaxf(dlt, 0.f) : fmaxf(-dlt, 0.f);
+            const float a = m ? e * wacc[k] : e;
+            sacc[k] = km == 0 ? a : sacc[k] + a;
+            wacc[k] = 0.f;
+        }
+    };
     if (m) {
         const int R = g.R;
         for (int i = tid; i < 2 * R + 1; i += AN_THREADS) gs[i] = taps.g[i];
@@ -143,28 +174,40 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __
             const int j = e / AN_TW, k = e % AN_TW;
             AW[e] = w0 + k < g.W ? an_band(gs, R, w0 + k, cW0 + j, g.fW) : 0.f;
         }
-        const float* mb = m + b * ((int64_t)g.d * g.h * g.w);
-        for (int j = 0; j < nD; ++j) {
-            // (cD0 + j < d, cH0 + ih < h, cW0 + iw < w by the construction of nD, nH, nW)
-            for (int e = tid; e < nH * nW; e += AN_THREADS) {
-                const int ih = e / nW, iw = e - ih * nW;
-                ms[ih * g.nWm + iw] = mb[((int64_t)(cD0 + j) * g.h + (cH0 + ih)) * g.w + (cW0 + iw)];
-            }
-            __syncthreads();      // (the first pass: the band tables too)
-            for (int e = tid; e < nH * AN_TW; e += AN_THREADS) {
-                const int ih = e / AN_TW, c = e % AN_TW;
-                float acc = 0.f;
-                for (int iw = 0; iw < nW; ++iw) acc = fmaf(AW[iw * AN_TW + c], ms[ih * g.nWm + iw], acc);
-                T1[e] = acc;
-            }
-            __syncthreads();
-            float s = 0.f;
-            for (int ih = 0; ih < nH; ++ih) s = fmaf(AH[ih * AN_TH + hl], T1[ih * AN_TW + wl], s);
+        const int members = ENS ? M.K : 1;
+        for (int km = 0; km < members; ++km) {
+            if constexpr (ENS) load_member(km);
+            // (a later member's first plane is the next plane of the two-barrier pattern below: ms and T1 are free again after the second barrier)
+            const float* mb = m + (ENS ? km * M.m_stride : (int64_t)0) + b * ((int64_t)g.d * g.h * g.w);
+            for (int j = 0; j < nD; ++j) {
+                // (cD0 + j < d, cH0 + ih < h, cW0 + iw < w by the construction of nD, nH, nW)
+                for (int e = tid; e < nH * nW; e += AN_THREADS) {
+                    const int ih = e / nW, iw = e - ih * nW;
+                    ms[ih * g.nWm + iw] = mb[((int64_t)(cD0 + j) * g.h + (cH0 + ih)) * g.w + (cW0 + iw)];
+                }
+                __syncthreads();      // (the first pass: the band tables too)
+                for (int e = tid; e < nH * AN_TW; e += AN_THREADS) {
+                    const int ih = e / AN_TW, c = e % AN_TW;
+                    float acc = 0.f;
+                    for (int iw = 0; iw < nW; ++iw) acc = fmaf(AW[iw * AN_TW + c], ms[ih * g.nWm + iw], acc);
+                    T1[e] = acc;
+                }
+                __syncthreads();
+                float s = 0.f;
+                for (int ih = 0; ih < nH; ++ih) s = fmaf(AH[ih * AN_TH + hl], T1[ih * AN_TW + wl], s);
 #pragma unroll
-            for (int k = 0; k < AN_LD; ++k) wacc[k] = fmaf(AD[j * AN_LD + k], s, wacc[k]);
+                for (int k = 0; k < AN_LD; ++k) wacc[k] = fmaf(AD[j * AN_LD + k], s, wacc[k]);
+            }
+            if constexpr (ENS) fold(km);
         }
     } else {
         __syncthreads();          // the histogram is clear
+        if constexpr (ENS) {
+            for (int km = 0; km < M.K; ++km) {
+                load_member(km);
+                fold(km);
+            }
+        }
     }
 
     double bs = 0.0;
@@ -175,7 +218,7 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __
         if (valid && k < np) {
             const float dlt = xv[k] - rv[k];
             const float e = g.mode == SA_ANOMALY_ABS ? fabsf(dlt) : g.mode == SA_ANOMALY_POSITIVE ? fmaxf(dlt, 0.f) : fmaxf(-dlt, 0.f);
-            const float a = m ? e * wacc[k] : e;
+            const float a = ENS ? sacc[k] * M.inv_K : m ? e * wacc[k] : e;
             a_out[base + k * plane] = a;
             bs += (double)a;
             bm = fmaxf(bm, a);
@@ -219,6 +262,21 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __
         const uint32_t v = hist[i];
         if (v) atomicAdd(res + 8 + i, (unsigned long long)v);
     }
+}
+
+__global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ m,
+                                                                 const unsigned char* __restrict__ label, float* __restrict__ a_out, const AnGeom g,
+                                                                 const AnTaps taps, unsigned long long* __restrict__ part,
+                                                                 unsigned long long* __restrict__ results) {
+    anomaly_map_body<false>(x, r, m, label, a_out, g, taps, part, results, AnMembers{1, 1.f, 0, 0});
+}
+
+__global__ __launch_bounds__(AN_THREADS) void anomaly_map_ensemble_kernel(const float* __restrict__ x, const float* __restrict__ r,
+                                                                          const float* __restrict__ m, const unsigned char* __restrict__ label,
+                                                                          float* __restrict__ a_out, const AnGeom g, const AnTaps taps,
+                                                                          unsigned long long* __restrict__ part,
+                                                                          unsigned long long* __restrict__ results, const AnMembers M) {
+    anomaly_map_body<true>(x, r, m, label, a_out, g, taps, part, results, M);
 }
 
 // results[b][0] = sum a, [1] = max a (both as doubles), [2..4] = TP, FP, FN, [8] and [8 + 256] = bin 0 of the two classes: one block per volume, lanes
@@ -328,6 +386,34 @@ extern "C" int sa_anomaly_map(const float* x, const float* r, const float* m, co
     }
     SA_LAUNCH(anomaly_map_kernel, dim3((unsigned)g.nblk, (unsigned)B), dim3(AN_THREADS), (size_t)an_lds_bytes(g), st, x, r, m, label, a_out, g, taps,
               (unsigned long long*)ws, (unsigned long long*)results);
+    SA_CHECK_LAUNCH();
+    SA_LAUNCH(anomaly_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const unsigned long long*)ws, g.nblk, (unsigned long long*)results);
+    SA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sa_anomaly_map_ensemble(const float* x, const float* r, int64_t r_member_stride, const float* m, int64_t m_member_stride,
+                                       const unsigned char* label, float* a_out, const sa_anomaly_params* params, int members, void* results, void* ws,
+                                       void* stream) {
+    if (!x || !r || !a_out || !params || !results || !ws || (((uintptr_t)results) & 7u) != 0 || (((uintptr_t)ws) & 7u) != 0) return SA_EINVAL;
+    if (members < 1 || members > SA_ANOMALY_MAX_MEMBERS) return SA_EINVAL;
+    AnGeom g;
+    const int rc = an_plan(*params, m != nullptr, g);
+    if (rc) return rc;
+    const int B = params->B;
+    // a member's extent in elements (an_plan: B <= 65535, D H W < 2^31, d h w <= D H W)
+    if (r_member_stride < (int64_t)B * g.D * g.H * g.W) return SA_EINVAL;
+    if (m && m_member_stride < (int64_t)B * g.d * g.h * g.w) return SA_EINVAL;
+    AnTaps taps;
+    for (int i = 0; i < AN_TAPS; ++i) taps.g[i] = i < 2 * params->R + 1 ? params->taps[i] : 0.f;
+    const AnMembers M{members, (float)(1.0 / (double)members), r_member_stride, m ? m_member_stride : (int64_t)0};
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(results, 0, (size_t)B * AN_WORDS * 8, st) != hipSuccess) {
+        g_last_error = hipGetLastError();
+        return (int)g_last_error;
+    }
+    SA_LAUNCH(anomaly_map_ensemble_kernel, dim3((unsigned)g.nblk, (unsigned)B), dim3(AN_THREADS), (size_t)an_lds_bytes(g), st, x, r, m, label, a_out, g,
+              taps, (unsigned long long*)ws, (unsigned long long*)results, M);
     SA_CHECK_LAUNCH();
     SA_LAUNCH(anomaly_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const unsigned long long*)ws, g.nblk, (unsigned long long*)results);
     SA_CHECK_LAUNCH();
