@@ -528,6 +528,31 @@ int sa_favor_features_project_bwd(const float *dfeat, const float *feat, const f
                                   int is_query, float *dsrc, const void *gmax_ws, float *tsum_ws, int64_t rows, int m, int LDF, int dh, void *stream);
 int sa_favor_dden(const float *dout, const float *out, int stride, int off, int G, int dv, const float *inv, float *dden, int64_t rows,
                   void *stream);
+/* Generalized (ReLU) attention -- generalized_attention=True of the reference (run_transformer.py:81, src/networks/transformers/performer.py:97-98,207-208:
+ * performer_pytorch FastAttention then maps q and k through generalized_kernel with kernel_fn = nn.ReLU() instead of softmax_kernel).  Restated from
+ * performer-pytorch 1.0.11, unpinned (csrc/favor_generalized.hip):  phi(x) = relu(dd) + 1e-3, dd = x @ proj^T with the data normaliser folded into proj; the
+ * same map for queries and keys, no ratio, no |x|^2 term, no maximum.  Feature columns [m, LDF) are ZERO.  Derivative: d dd = d phi * [phi > 1e-3f], read
+ * from the stored phi (it differs from [dd > 0] only for 0 < dd < ~6e-11, where relu(dd) + 1e-3f rounds to 1e-3f).  None of these launches uses atomics.
+ * sa_favor_generalized_features_fwd / _bwd : fp32 parity mode, elementwise on [rows][LDF] (LDF % 4 == 0) around the exact-fp32 projection GEMMs:
+ *                 feat = relu(dd) + 1e-3f;  ddd = dfeat * [feat > 1e-3f];  columns >= m of feat / ddd are written as zeros whatever the inputs hold there.
+ * sa_favor_generalized_project_features : throughput mode, sa_favor_project with the map applied to the accumulators (dd is never written).  x rows are head
+ *                 blocks as for sa_favor_project.  ngroups (1 or 2) operands in one launch: operand gi is read x_goff and written feat_goff ELEMENTS behind
+ *                 operand 0 (q and k as column blocks of the fused qkv matrix), both multiples of 4.
+ * sa_favor_generalized_project_bwd : throughput mode, dx = (dfeat * [feat > 1e-3f])[:, :m] @ proj into the head blocks of dx (nothing else of dx is touched);
+ *                 operand gi of dfeat AND feat lies feat_goff, of dx dx_goff elements behind operand 0.  dh = 64, LDF % 16 == 0, LDF <= 272 for both.
+ * sa_favor_generalized_step : the O(N) decode step of the global heads (cf. sa_favor_step): E [B*G, LDF, dh] += phi(k_t) (x) v_t, Ez [B*G, LDF] += phi(k_t),
+ *                 out = (phi(q_t) . E) / (phi(q_t) . (Ez + 1e-6)) -- the normaliser of sa_favor_scan_a_norm, so the step equals the training forward.  E and Ez
+ *                 are plain running sums (zero at the start; no smax / kmax / V1); dd [2, B*G, LDF] scratch.  pos: the device position word of the sampler;
+ *                 the arithmetic does not depend on it (no host synchronisation, two launches in a chain: capturable).  SA_EUNSUPPORTED for dh != 64 or m > 272. */
+int sa_favor_generalized_features_fwd(const float *dd, float *feat, int64_t rows, int m, int LDF, void *stream);
+int sa_favor_generalized_features_bwd(const float *dfeat, const float *feat, float *ddd, int64_t rows, int m, int LDF, void *stream);
+int sa_favor_generalized_project_features(const float *x, int x_stride, int heads, const float *proj, float *feat, int64_t rows, int m, int LDF, int dh,
+                                          int ngroups, int64_t x_goff, int64_t feat_goff, void *stream);
+int sa_favor_generalized_project_bwd(const float *dfeat, const float *feat, const float *proj, float *dx, int dx_stride, int heads, int64_t rows, int m,
+                                     int LDF, int dh, int ngroups, int64_t feat_goff, int64_t dx_goff, void *stream);
+int sa_favor_generalized_step(const float *q, int q_stride, int q_off, const float *k, int k_stride, int k_off, const float *v, int v_stride, int v_off,
+                              const float *proj, int B, int G, int dh, int m, int LDF, float *dd, float *E, float *Ez, const int *pos, float *out,
+                              int out_stride, int out_off, void *stream);
 /* rotary embedding of the local heads (local-attention >= 1.2); transpose=1 applies the adjoint (backward) */
 int sa_rotary(const float *x, int stride, int off, int L, int dh, const float *cosb, const float *sinb, float *y, int y_stride, int y_off,
               int N, int64_t R, int transpose, int accumulate, void *stream);

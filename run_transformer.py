@@ -267,6 +267,10 @@ def run(argv):
         resample_threshold(cfg["resample_threshold"])     # refuses before anything touches the device
     from synthanatomy_amd.utils.transformer import conditioning_flags
     cfg["conditionings"] = conditioning_flags(cfg["conditioning_path"], cfg["conditionings"], cfg["conditioning_type"])   # they act or refuse: never ignored
+    if cfg["generalized_attention"]:
+        # --generalized_attention=True acts in every mode (ReLU feature map); with a dropout flag it refuses by name before anything touches the device
+        from synthanatomy_amd.networks.transformers.performer import refuse_generalized_options
+        refuse_generalized_options(True, emb_dropout=cfg["emb_dropout"], ff_dropout=cfg["ff_dropout"], attn_dropout=cfg["attn_dropout"])
     rank, local, world = init_distributed()
     cfg.update(rank=rank, local_rank=local, world_size=world)
     torch.manual_seed(cfg["seed"])

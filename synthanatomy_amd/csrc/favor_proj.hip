@@ -4,8 +4,7 @@
 // hi / lo tiles (split_bf16.h: hi*hi + hi*lo + lo*hi on mfma_f32_16x16x32_bf16, fp32 accumulate, ~1e-5 relative), streams rows straight from
 // global memory into MFMA operands and writes 16-byte pieces of the result rows from the accumulators.  Traffic = read x, write dd (forward);
 // read ddd (+ addend), write dx (adjoint).  The fp32 parity mode of the engine keeps the exact-fp32 GEMM.
-#include "sa_common.h"
-#include "split_bf16.h"
+#include "favor_proj_common.h"
 
 namespace sa {
 
@@ -22,45 +21,6 @@ struct ProjArgs {
     float c2half, ratio, eps;
     int32_t heads;         // x / out rows are head blocks of wider rows: row r lives at (r / heads) * stride + (r % heads) * 64
 };
-
-__device__ __forceinline__ int64_t proj_row_off(int64_t r, int heads, int stride) { return (r / heads) * stride + (r % heads) * 64; }
-
-// projection rows [0, nrows) -> hi / lo tiles [nrows][64] bf16 in the lroff() layout (rows >= m are zero)
-// PERM: tile row rho holds projection row pi(rho), pi(ks*32 + b*16 + 4g + r) = ks*32 + 8g + 4b + r.  The transposing reads hand lane group g the
-// tile rows {4g..4g+3, 16+4g..} of a 32-row block as its eight reduction steps; with pi those are the EIGHT CONSECUTIVE features ks*32 + 8g .. +7,
-// so the gradient rows that multiply them are read as 32 contiguous bytes per lane (a full 128-byte line per row and 32-feature block).
-template <bool PERM = false>
-__device__ __forceinline__ void proj_stage(unsigned char* hi, unsigned char* lo, const float* proj, int m, int nrows, int tid) {
-    // all loads first (nrows <= 288: at most 18 pieces of 16 bytes per thread), then the splits: a load -> split -> store loop with a run-time
-    // trip count pays the L2 round trip once per iteration (18 us per block, measured as 2/3 of the adjoint kernel)
-    float4 v[18];
-#pragma unroll
-    for (int t = 0; t < 18; ++t) {
-        const int idx = tid + 256 * t, rho = min(idx >> 4, nrows - 1), c4 = idx & 15;
-        const int f = PERM ? (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3) : rho;
-        v[t] = *(const float4*)(proj + (int64_t)min(f, m - 1) * 64 + c4 * 4);
-    }
-#pragma unroll
-    for (int t = 0; t < 18; ++t) {
-        const int idx = tid + 256 * t, rho = idx >> 4, c4 = idx & 15;
-        if (rho < nrows) {
-            const int f = PERM ? (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3) : rho;
-            const float k = f < m ? 1.f : 0.f;
-            uint2 h, l;
-            split_pair(v[t].x * k, v[t].y * k, h.x, l.x);
-            split_pair(v[t].z * k, v[t].w * k, h.y, l.y);
-            const uint32_t o = lroff(rho, c4 * 4);
-            *(uint2*)(hi + o) = h;
-            *(uint2*)(lo + o) = l;
-        }
-    }
-}
-
-__device__ __forceinline__ float4 proj_keep(float4 x, bool keep) {
-    const uint32_t mk = keep ? 0xffffffffu : 0u;
-    return make_float4(__uint_as_float(__float_as_uint(x.x) & mk), __uint_as_float(__float_as_uint(x.y) & mk), __uint_as_float(__float_as_uint(x.z) & mk),
-                       __uint_as_float(__float_as_uint(x.w) & mk));
-}
 
 // forward: block = 128 rows, wave = 32 rows (two MFMA column sets); D[i = feature][j = row]
 // QFEAT: the QUERY feature map phi = ratio (exp(dd - |x|^2 c^2 / 2 - rowmax) + eps) in the same launch: the row maximum is known after one walk over

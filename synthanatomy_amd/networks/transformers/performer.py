@@ -131,10 +131,11 @@ class FastAttention(nn.Module):
 
 
 class SelfAttention(nn.Module):
-    def __init__(self, dim, heads, dim_head, local_heads, local_window_size, nb_features, qkv_bias, attn_out_bias):
+    def __init__(self, dim, heads, dim_head, local_heads, local_window_size, nb_features, qkv_bias, attn_out_bias, generalized=False):
         super().__init__()
         inner = dim_head * heads
         self.heads, self.global_heads, self.dim_head = heads, heads - local_heads, dim_head
+        self.generalized = bool(generalized)     # FastAttention(generalized_attention=True, kernel_fn=nn.ReLU()): phi = relu(dd) + 1e-3 (csrc/favor_generalized.hip)
         self.fast_attention = FastAttention(dim_head, nb_features)
         self.local_attn = LocalAttention(local_window_size, dim_head) if local_heads > 0 else None
         self.to_q = nn.Linear(dim, inner, bias=qkv_bias)
@@ -219,6 +220,19 @@ class ProjectionUpdater(nn.Module):
         self.calls_since_last_redraw += 1
 
 
+def refuse_generalized_options(generalized_attention, kernel_fn=None, **dropouts):
+    """generalized_attention=True acts with kernel_fn = nn.ReLU() and without dropout, or refuses by name: another kernel_fn has no kernels here, and the
+    combination with a non-zero ff_dropout / attn_dropout / emb_dropout is out of scope.  ``kernel_fn=None``: not given (the CLI has no such flag)."""
+    if not generalized_attention:
+        return
+    if kernel_fn is not None and not isinstance(kernel_fn, nn.ReLU):
+        name = type(kernel_fn).__name__ if isinstance(kernel_fn, nn.Module) else getattr(kernel_fn, "__name__", repr(kernel_fn))
+        raise NotImplementedError(f"generalized_attention=True is implemented for kernel_fn=nn.ReLU() only, but got kernel_fn={name}")
+    for flag, p in dropouts.items():
+        if float(p) != 0.0:
+            raise NotImplementedError(f"generalized_attention=True combined with {flag}={p} is not implemented: use {flag}=0 or generalized_attention=False")
+
+
 class BasePerformer(nn.Module):
     """Parameter tree of performer_pytorch.Performer (the argument order of performer.py:194-219)."""
 
@@ -226,11 +240,12 @@ class BasePerformer(nn.Module):
                  reversible, ff_chunks, generalized_attention, kernel_fn, use_scalenorm, use_rezero, ff_glu, ff_dropout, attn_dropout, cross_attend,
                  no_projection, auto_check_redraw, qkv_bias, attn_out_bias):
         super().__init__()
-        unsupported = dict(reversible=reversible, generalized_attention=generalized_attention, use_scalenorm=use_scalenorm, ff_glu=ff_glu,
-                           cross_attend=cross_attend, no_projection=no_projection)
+        unsupported = dict(reversible=reversible, use_scalenorm=use_scalenorm, ff_glu=ff_glu, cross_attend=cross_attend, no_projection=no_projection)
         bad = [k for k, v in unsupported.items() if v]
         if bad or not causal or ff_chunks != 1:
             raise NotImplementedError(f"performer on MI355X implements the causal ReZero / pre-LayerNorm FAVOR+ configuration; unsupported: {bad}")
+        refuse_generalized_options(generalized_attention, kernel_fn, ff_dropout=ff_dropout, attn_dropout=attn_dropout)
+        self.generalized = bool(generalized_attention)
         for name, p in (("ff_dropout", ff_dropout), ("attn_dropout", attn_dropout)):
             if not 0.0 <= float(p) < 1.0:
                 raise ValueError(f"{name} must lie in [0, 1) (nn.Dropout's keep probability 1 - p must be positive), got {p}")
@@ -245,7 +260,7 @@ class BasePerformer(nn.Module):
         layers = nn.ModuleList([])
         for lh in local_attn_heads:
             layers.append(nn.ModuleList([
-                wrap(SelfAttention(dim, heads, dim_head, lh, local_window_size, nb_features, qkv_bias, attn_out_bias)),
+                wrap(SelfAttention(dim, heads, dim_head, lh, local_window_size, nb_features, qkv_bias, attn_out_bias, self.generalized)),
                 wrap(Chunk(FeedForward(dim, ff_mult))),
             ]))
         self.net = SequentialSequence(layers)
@@ -312,6 +327,7 @@ class _LayerEngine:
         self.sa, self.ff = sa, ff
         self.H, self.G, self.dh = sa.heads, sa.global_heads, sa.dim_head
         self.L = self.H - self.G
+        self.generalized = sa.generalized and self.G > 0      # (a layer without global heads has nothing generalized to run)
         self.m = sa.fast_attention.nb_features
         self.LDF = _ru(self.m, 16)
         if self.G > 0 and (self.LDF > 272 or self.dh != 64):
@@ -405,7 +421,7 @@ class _LayerEngine:
 
     def _fused_favor(self):
         """throughput mode: FAVOR+ with the feature maps recomputed on chip (csrc/favor_fused.hip) -- no [B N G, 272] tensor in HBM"""
-        return not self._xf and self.G > 0 and self.dh == 64 and self.m <= 272 and not debug.host("no_fused_favor")
+        return not self._xf and self.G > 0 and self.dh == 64 and self.m <= 272 and not self.generalized and not debug.host("no_fused_favor")
 
     def _rot_tables(self, N, dev):
         if self._rot is None or self._rot[0] != (N, dev):
@@ -567,6 +583,8 @@ class _LayerEngine:
         lib, st, dev, f32 = _ffi.lib(), _ffi.stream(), q.device, torch.float32
         R, G, dh, m, LDF, inner = B * N, self.G, self.dh, self.m, self.LDF, self.H * self.dh
         pop = self._proj_op()
+        if self.generalized:
+            return self._favor_generalized_fwd(q, k, v, qs, attn, B, N, tape, sv)
         if self._xf:   # fp32 parity mode: exact-fp32 GEMM on contiguous copies of the global-head columns
             qg = q[:, : G * dh].contiguous()
             kg = k[:, : G * dh].contiguous()
@@ -597,6 +615,40 @@ class _LayerEngine:
         _ffi.check(lib.sa_favor_scan_a_norm(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dh,
                                      _ffi.ptr(ws), self._xf, st), "sa_favor_scan_a_norm")
         sv.update(qg=qg, kg=kg, ddq=ddq, ddk=ddk, qf=qf, kf=kf, gws=gws, inv=inv, scan_state=ws if tape is not None else None)
+
+    @staticmethod
+    def _column_blocks(a, b, inner):
+        """a | b are column blocks `inner` floats apart of one fp32 matrix (q | k of the fused qkv launch, dq | dk of its gradient): one launch serves both"""
+        return b.data_ptr() - a.data_ptr() == inner * 4 and a.stride(0) == b.stride(0)
+
+    def _favor_generalized_fwd(self, q, k, v, qs, attn, B, N, tape, sv):
+        """generalized (ReLU) attention on the chunked route, both dtype modes (csrc/favor_generalized.hip): phi = relu(dd) + 1e-3 for q and k alike, then
+        the causal scan exactly as for the softmax features.  The tape keeps phi(q) | phi(k) only: the backward reads its masks from them."""
+        lib, st, dev, f32 = _ffi.lib(), _ffi.stream(), q.device, torch.float32
+        R, G, dh, m, LDF, inner = B * N, self.G, self.dh, self.m, self.LDF, self.H * self.dh
+        pop = self._proj_op()
+        qkf = torch.empty(2, R * G, LDF, dtype=f32, device=dev)
+        qf, kf = qkf[0], qkf[1]
+        if self._xf:   # fp32 parity mode: exact-fp32 GEMM on contiguous copies of the global-head columns, then the elementwise map
+            for src, feat, nm in ((q, qf, "q"), (k, kf, "k")):
+                dd = pop.fprop(src[:, : G * dh].contiguous().view(1, 1, 1, R * G, dh), out_channels_stride=LDF, use_bias=False).view(R * G, LDF)
+                _ffi.check(lib.sa_favor_generalized_features_fwd(_ffi.ptr(dd), _ffi.ptr(feat), R * G, m, LDF, st), f"sa_favor_generalized_features_fwd({nm})")
+        else:          # throughput mode: projection and map in one launch, reading the head blocks of q / k in place (dd is never written)
+            ps = self._pop[2]
+            if self._column_blocks(q, k, inner):
+                _ffi.check(lib.sa_favor_generalized_project_features(_ffi.ptr(q), qs, G, _ffi.ptr(ps), _ffi.ptr(qkf), R * G, m, LDF, dh, 2, inner, R * G * LDF, st),
+                    "sa_favor_generalized_project_features(q|k)")
+            else:
+                for src, feat, nm in ((q, qf, "q"), (k, kf, "k")):
+                    _ffi.check(lib.sa_favor_generalized_project_features(_ffi.ptr(src), qs, G, _ffi.ptr(ps), _ffi.ptr(feat), R * G, m, LDF, dh, 1, 0, 0, st),
+                        f"sa_favor_generalized_project_features({nm})")
+        ws = self._scan_ws(B, N, G, dev)
+        if tape is not None:   # training: the chunk states are kept for the dq' scan of the backward pass
+            ws = torch.empty_like(ws)
+        inv = torch.empty(R * G, dtype=f32, device=dev)
+        _ffi.check(lib.sa_favor_scan_a_norm(_ffi.ptr(kf), _ffi.ptr(qf), _ffi.ptr(v), qs, 0, _ffi.ptr(attn), inner, 0, _ffi.ptr(inv), 1e-6, B, N, G, LDF, dh,
+                                     _ffi.ptr(ws), self._xf, st), "sa_favor_scan_a_norm")
+        sv.update(qf=qf, kf=kf, inv=inv, scan_state=ws if tape is not None else None)
 
     # ---------------------------------------------------------------------------------------------- stateful decoding (one position)
     def _local_fwd_prep(self, q, k, v, qs, attn, attn_lp, B, N, R, dev, sv):
@@ -634,6 +686,12 @@ class _LayerEngine:
         value caches of the local heads."""
         G, L, dh, LDF = self.G, self.L, self.dh, self.LDF
         f32 = torch.float32
+        if self.generalized:      # plain running sums: no stabiliser (smax / kmax), no eps part (V1); the local heads' caches as below
+            stt = dict(dd=torch.zeros(2, B * G, LDF, dtype=f32, device=dev), E=torch.empty(B * G, LDF * dh, dtype=f32, device=dev),
+                       Ez=torch.empty(B * G, LDF, dtype=f32, device=dev), kc=torch.empty(B, max(L, 1), N, dh, dtype=f32, device=dev),
+                       vc=torch.empty(B, max(L, 1), N, dh, dtype=f32, device=dev))
+            self.reset_state(stt)
+            return stt
         stt = dict(smax=torch.empty(2, dtype=f32, device=dev), kmax=torch.empty(2, dtype=torch.int32, device=dev),
                    dd=torch.zeros(2, max(B * G, 1), LDF, dtype=f32, device=dev),
                    E=torch.empty(max(B * G, 1), LDF * dh, dtype=f32, device=dev), Ez=torch.empty(max(B * G, 1), LDF, dtype=f32, device=dev),
@@ -696,7 +754,7 @@ class _LayerEngine:
         qkv = torch.empty(B, 3 * inner, dtype=f32, device=dev)
         self._gemv(xa, [sa.to_q, sa.to_k, sa.to_v], qkv)
         attn = torch.empty(B, inner, dtype=f32, device=dev)
-        merged = G > 0 and L > 0 and dh == 64 and (2 * self.W + 3) // 4 <= 256
+        merged = G > 0 and L > 0 and dh == 64 and (2 * self.W + 3) // 4 <= 256 and not self.generalized
         if merged:
             # both kinds of heads in TWO launches: [projections | local heads over four key segments], [FAVOR+ update | combine of the segments]
             self._proj_op()
@@ -704,7 +762,12 @@ class _LayerEngine:
             _ffi.check(lib.sa_attn_step(_ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(self._pop[2]), B, G, L, dh, m, LDF, _ffi.ptr(stt["smax"]), _ffi.ptr(stt["kmax"]),
                                  _ffi.ptr(stt["dd"]), _ffi.ptr(stt["E"]), _ffi.ptr(stt["Ez"]), _ffi.ptr(stt["V1"]), _ffi.ptr(cosb), _ffi.ptr(sinb), _ffi.ptr(stt["kc"]),
                                  _ffi.ptr(stt["vc"]), N, self.W, _ffi.ptr(stt["lpart"]), _ffi.ptr(pos), _ffi.ptr(attn), inner, st), "sa_attn_step")
-        if G > 0 and not merged:
+        if self.generalized:
+            self._proj_op()
+            _ffi.check(lib.sa_favor_generalized_step(_ffi.ptr(qkv), 3 * inner, 0, _ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(qkv), 3 * inner, 2 * inner,
+                                                     _ffi.ptr(self._pop[2]), B, G, dh, m, LDF, _ffi.ptr(stt["dd"]), _ffi.ptr(stt["E"]), _ffi.ptr(stt["Ez"]),
+                                                     _ffi.ptr(pos), _ffi.ptr(attn), inner, 0, st), "sa_favor_generalized_step")
+        elif G > 0 and not merged:
             self._proj_op()
             ps = self._pop[2]    # projection matrix with the data normaliser folded in
             _ffi.check(lib.sa_favor_step(_ffi.ptr(qkv), 3 * inner, 0, _ffi.ptr(qkv), 3 * inner, inner, _ffi.ptr(qkv), 3 * inner, 2 * inner, _ffi.ptr(ps), B, G, dh, m, LDF,
@@ -828,7 +891,10 @@ class _LayerEngine:
         dden = torch.empty(R * G, dtype=f32, device=dev)
         _ffi.check(lib.sa_favor_dden(_ffi.ptr(dattn), _ffi.ptr(attn), inner, 0, G, dh, _ffi.ptr(inv), _ffi.ptr(dden), R * G, st), "sa_favor_dden")
         ws = self._scan_ws(B, N, G, dev)
-        dqf, dkf = torch.empty_like(qf), torch.empty_like(kf)
+        if self.generalized:   # one tensor, like qf | kf of its forward: the adjoint takes both sides in one launch
+            dqf, dkf = torch.empty(2, R * G, LDF, dtype=f32, device=dev).unbind(0)
+        else:
+            dqf, dkf = torch.empty_like(qf), torch.empty_like(kf)
         kept = sv.get("scan_state")   # the forward's chunk states: same (a = k', b = v) -> no state / prefix passes for dq'
         _ffi.check(lib.sa_favor_scan_b_cum(_ffi.ptr(kf), _ffi.ptr(v), qs, 0, None, _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dqf), _ffi.ptr(dden), 1, 1e-6,
                                     B, N, G, LDF, dh, 0, _ffi.ptr(kept if kept is not None else ws), (1 if kept is not None else 0) | self._xf, st),
@@ -840,6 +906,8 @@ class _LayerEngine:
         _ffi.check(lib.sa_favor_scan_a_state(_ffi.ptr(qf), _ffi.ptr(kf), _ffi.ptr(dattn), inner, 0, _ffi.ptr(inv), _ffi.ptr(dv), qs, 0, None, B, N, G, LDF, dh, 1, 0,
                                       _ffi.ptr(ws), 3 | self._xf, st), "sa_favor_scan_a_state(dv)")
         pop = self._proj_op()
+        if self.generalized:
+            return self._favor_generalized_bwd(sv, dqf, dkf, dq, dk, R)
         tsum = torch.empty(R * G, dtype=f32, device=dev)
         if self._xf:   # fp32 parity mode: feature-map backward, then the exact-fp32 dgrad GEMM with the -|x|^2 part as addend
             dddq, dddk = torch.empty_like(qf), torch.empty_like(kf)
@@ -860,6 +928,28 @@ class _LayerEngine:
                                                   None, None, R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(q)")
             _ffi.check(lib.sa_favor_features_project_bwd(_ffi.ptr(dkf), _ffi.ptr(kf), _ffi.ptr(sv["ddk"]), _ffi.ptr(sv["kg"]), qs, G, _ffi.ptr(ps), 0, _ffi.ptr(dk),
                                                   _ffi.ptr(sv["gws"]), _ffi.ptr(tsum), R * G, m, LDF, dh, st), "sa_favor_features_project_bwd(k)")
+
+    def _favor_generalized_bwd(self, sv, dqf, dkf, dq, dk, R):
+        """d phi(q) | d phi(k) -> the global-head columns of dq | dk: d dd = d phi [phi > 1e-3] (the mask read from the saved features), then the projection adjoint"""
+        lib, st = _ffi.lib(), _ffi.stream()
+        G, dh, m, LDF, inner = self.G, self.dh, self.m, self.LDF, self.H * self.dh
+        qf, kf = sv["qf"], sv["kf"]
+        pop = self._proj_op()
+        if self._xf:   # fp32 parity mode: the elementwise mask, then the exact-fp32 dgrad GEMM (no addend: the map has no |x|^2 term)
+            for dfeat, feat, dst, nm in ((dqf, qf, dq, "q"), (dkf, kf, dk, "k")):
+                ddd = torch.empty_like(feat)
+                _ffi.check(lib.sa_favor_generalized_features_bwd(_ffi.ptr(dfeat), _ffi.ptr(feat), _ffi.ptr(ddd), R * G, m, LDF, st),
+                    f"sa_favor_generalized_features_bwd({nm})")
+                dst[:, : G * dh] = pop.dgrad(ddd.view(1, 1, 1, R * G, LDF), (1, 1, R * G), fwd_out_stride=LDF).view(R, G * dh)
+            return
+        ps, qs, goff = self._pop[2], dq.stride(0), R * G * LDF
+        if self._column_blocks(dq, dk, inner) and kf.data_ptr() - qf.data_ptr() == goff * 4 and dkf.data_ptr() - dqf.data_ptr() == goff * 4:
+            _ffi.check(lib.sa_favor_generalized_project_bwd(_ffi.ptr(dqf), _ffi.ptr(qf), _ffi.ptr(ps), _ffi.ptr(dq), qs, G, R * G, m, LDF, dh, 2, goff, inner, st),
+                "sa_favor_generalized_project_bwd(q|k)")
+        else:
+            for dfeat, feat, dst, nm in ((dqf, qf, dq, "q"), (dkf, kf, dk, "k")):
+                _ffi.check(lib.sa_favor_generalized_project_bwd(_ffi.ptr(dfeat), _ffi.ptr(feat), _ffi.ptr(ps), _ffi.ptr(dst), qs, G, R * G, m, LDF, dh, 1, 0, 0, st),
+                    f"sa_favor_generalized_project_bwd({nm})")
 
     def bwd(self, dx2, sv, B, N, gc: GradCtx):
         self._sync()
@@ -1216,6 +1306,7 @@ class Performer(TransformerBase):
         compute_dtype: torch.dtype = torch.float32,
     ):
         super().__init__()
+        refuse_generalized_options(generalized_attention, kernel_fn, ff_dropout=ff_dropout, attn_dropout=attn_dropout, emb_dropout=emb_dropout)
         assert 0 <= sum([rotary_position_emb, fixed_position_emb, axial_position_emb]) <= 1, (
             f"rotary_position_emb, fixed_position_emb and axial_position_emb are exclusive, but received "
             f"{rotary_position_emb} {fixed_position_emb} and {axial_position_emb}."
