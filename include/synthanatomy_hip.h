@@ -380,6 +380,31 @@ int64_t sa_anomaly_map_workspace_bytes(const sa_anomaly_params *params);
 int sa_anomaly_map_ensemble(const float *x, const float *r, int64_t r_member_stride, const float *m, int64_t m_member_stride,
                             const unsigned char *label, float *a_out, const sa_anomaly_params *params, int members, void *results, void *ws,
                             void *stream);
+/* Connected components of a thresholded map, the size filter and lesion counts (metrics/components.py, run_vqvae.py --anomaly_min_component;
+ * csrc/components.hip; this project's own rule, no reference counterpart).  a [B, D, H, W] fp32 contiguous device tensor; label (NULL iff
+ * has_labels == 0) [B, D, H, W] bytes: class 1 where != 0; ids_out [B, D, H, W] int32.  params is read on the HOST.
+ *   foreground s(v) = [a(v) >= threshold] in fp32 (a NaN is background, a == threshold foreground);  components = the classes of foreground voxels
+ *   under adjacency by the offsets o in {-1, 0, 1}^3 with 1 <= |o|_1 <= 1, 2, 3 for connectivity 6, 18, 26;  a component's id is 1 + the smallest
+ *   linear index (d H W + h W + w) of its voxels;  ids_out = the id where the component has >= min_size voxels, 0 elsewhere (and on the background).
+ * results: B records of SA_COMPONENTS_RESULT_WORDS int64 words (every word is written): [0] components, [1] components kept, [2] foreground voxels,
+ * [3] kept voxels, [4] voxels of the largest component, [5], [6], [7] TP, FP, FN of the kept mask against the label, [8] lesions = components of the
+ * label volume under the same connectivity, [9] lesions with at least one kept voxel, [10] kept components with at least one class-1 voxel
+ * ([5..10] are 0 without labels), [11..15] 0.  Everything is an integer and the ids are canonical, so a volume's output is bitwise the same alone, in
+ * any batch and from call to call.  Five launches on the stream, no host synchronisation; the call overwrites every word of ws it reads.
+ * ws: sa_components_workspace_bytes(params) bytes, 16-byte aligned; results 8-byte aligned.
+ * SA_EINVAL (nothing launched) for null operands, a label pointer that disagrees with has_labels, a dim < 1, a connectivity outside {6, 18, 26},
+ * min_size < 1, a non-finite threshold, D H W >= 2^31 - 1; SA_EUNSUPPORTED for B > 65535. */
+enum { SA_COMPONENTS_TILE_D = 8, SA_COMPONENTS_TILE_H = 16, SA_COMPONENTS_TILE_W = 16, SA_COMPONENTS_RESULT_WORDS = 16 };
+typedef struct sa_components_params {
+    int32_t B, D, H, W;
+    int32_t connectivity;       /* 6 | 18 | 26 */
+    int32_t min_size;           /* >= 1 */
+    int32_t has_labels;
+    float threshold;
+} sa_components_params; /* 32 bytes */
+int sa_components(const float *a, const unsigned char *label, int32_t *ids_out, const sa_components_params *params, void *results, void *ws,
+                  void *stream);
+int64_t sa_components_workspace_bytes(const sa_components_params *params);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -59,6 +59,12 @@ its codes, one ``run_transformer.py --mode=healing`` outputs directory per order
 replaces; giving both is refused), every member is decoded on its own, and ``sa_anomaly_map_ensemble`` writes the mean of the members' weighted residuals
 as ``<name>_anomaly_map`` in one pass, with the scores of that mean; ``<name>_healed_reconstruction_m<k>`` is member k's decoding in flag order and
 ``anomaly_scores_rank<k>.csv`` gains a last column ``members``.  The other ``--anomaly_*`` flags are shared by the members.
+
+``--anomaly_min_component=<voxels>`` (MI355X-only; default None: nothing changes) cleans the segmentation ``[map >= --anomaly_threshold]``
+(which it needs) on the device: ``sa_components`` labels its connected components under ``--anomaly_connectivity=6|18|26`` (default 26), drops those
+below that many voxels and counts lesions; the single map and the ensemble map both go through it.  ``<name>_anomaly_segmentation`` ({0, 1}) is
+written like the map and the CSV gains ``components``, ``components_kept``, ``voxels_kept``, ``largest_component`` and, with ``--anomaly_labels``,
+``dice_cleaned``, ``lesions``, ``lesions_detected``, ``lesion_recall``, ``lesion_precision``, ``lesion_f1`` (before ``members``).
 """
 import os
 import sys
@@ -86,7 +92,7 @@ DEFAULTS = dict(
     output_ext=".npy", output_dtype="float32", perceptual_weights=None,
     codebook_restart_patience=None, codebook_restart_max=32,
     anomaly_codes=None, anomaly_weight="mask", anomaly_sigma=None, anomaly_residual="abs", anomaly_threshold=None, anomaly_hist_max=1.0, anomaly_labels=None,
-    anomaly_ensemble=None,
+    anomaly_ensemble=None, anomaly_min_component=None, anomaly_connectivity=26,
 )
 MODES = ["training", "extracting", "decoding", "anomaly"]
 
@@ -557,6 +563,22 @@ def _ensemble_specs(cfg):
 def _check_anomaly_flags(cfg):
     """the --anomaly_* flags act or refuse (before anything touches the device)"""
     from synthanatomy_amd.metrics.anomaly import MAX_MEMBERS, MAX_SIGMA, RESIDUALS
+    from synthanatomy_amd.metrics.components import CONNECTIVITIES
+    for name, given in (("anomaly_min_component", cfg["anomaly_min_component"] is not None),
+                        ("anomaly_connectivity", cfg["anomaly_connectivity"] != DEFAULTS["anomaly_connectivity"])):
+        if not given:
+            continue
+        flag = f"--{name}={cfg[name]}"
+        if cfg["mode"] != "anomaly":
+            raise ValueError(f"{flag}: the flag belongs to --mode=anomaly, not --mode={cfg['mode']}")
+        if cfg["anomaly_threshold"] is None:
+            raise ValueError(f"{flag}: the components are those of [map >= --anomaly_threshold], which is not given")
+    n = cfg["anomaly_min_component"]
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n < 1 or n >= 2 ** 31 - 1):
+        raise ValueError(f"--anomaly_min_component={n}: an integer >= 1 (voxels) or None is needed")
+    c = cfg["anomaly_connectivity"]
+    if isinstance(c, bool) or c not in CONNECTIVITIES:
+        raise ValueError(f"--anomaly_connectivity={c}: choices are 6, 18 and 26")
     specs = _ensemble_specs(cfg)
     if specs is not None:
         flag = f"--anomaly_ensemble={cfg['anomaly_ensemble']}"
@@ -658,6 +680,8 @@ def anomaly(cfg, rank, local, world, dev):
     """--mode=anomaly: every validation subject against the decoding of its healed codes, on the device from the scan to the scores."""
     import csv
     from synthanatomy_amd.metrics.anomaly import anomaly_map, anomaly_map_ensemble, average_precision, best_dice, dice_from_counts
+    from synthanatomy_amd.metrics.components import connected_components, lesion_scores
+    min_component = cfg["anomaly_min_component"]
     files = list_inputs(cfg["validation_subjects"])
     specs = _ensemble_specs(cfg)      # DESIGN 7.15: K healings per subject, one fused map; None: the single healing of 7.11
     if specs is None:
@@ -718,11 +742,19 @@ def anomaly(cfg, rank, local, world, dev):
                     amap, summ = anomaly_map_ensemble(x, block, torch.stack(wgts) if wgts[0] is not None else None, sigma=sigma,
                                                       residual=cfg["anomaly_residual"], labels=labels, threshold=cfg["anomaly_threshold"],
                                                       hist_max=cfg["anomaly_hist_max"])
+                seg = comp = None
+                if min_component is not None:      # the map, single or ensemble, is still on the device
+                    ids, comp = connected_components(amap, threshold=cfg["anomaly_threshold"], connectivity=int(cfg["anomaly_connectivity"]),
+                                                     min_size=min_component, labels=labels)
+                    seg = (ids > 0).float()
                 posts = ["healed_reconstruction"] if specs is None else [f"healed_reconstruction_m{k}" for k in range(len(members))]
                 if saver is None:
                     host = [rec.cpu().numpy() for rec in recs]
+                    seg_host = seg.cpu().numpy() if seg is not None else None
                     for j, (n, a_) in enumerate(zip(names, amap.cpu().numpy())):
                         save_npy(a_[0], cfg["outputs_directory"], n, "anomaly_map", np.float32)
+                        if seg_host is not None:
+                            save_npy(seg_host[j, 0], cfg["outputs_directory"], n, "anomaly_segmentation", np.float32)
                         for post, r_ in zip(posts, host):
                             save_npy(r_[j, 0], cfg["outputs_directory"], n, post, np.float32)
                 else:
@@ -730,8 +762,12 @@ def anomaly(cfg, rank, local, world, dev):
                     for j, (n, a_, h) in enumerate(zip(names, amap, headers)):
                         geom = nifti_output_geometry(h, cfg["roi"], canonical, a_.shape[-3:])
                         saver.save(a_[0], _output_path(cfg, n, "anomaly_map"), *geom)
+                        if seg is not None:
+                            saver.save(seg[j, 0], _output_path(cfg, n, "anomaly_segmentation"), *geom)
                         for post, rec in zip(posts, recs):
                             saver.save(rec[j, 0], _output_path(cfg, n, post), *geom)
+                if comp is not None:
+                    comp = {k: v.cpu().numpy() for k, v in comp.items() if v is not None}
                 sums, maxs, hist = summ["sum"].cpu().numpy(), summ["max"].cpu().numpy(), summ["hist"].cpu().numpy()
                 counts = [summ[k].cpu().numpy() for k in ("tp", "fp", "fn")] if summ["tp"] is not None else None
                 for j, n in enumerate(names):
@@ -740,6 +776,14 @@ def anomaly(cfg, rank, local, world, dev):
                         bd, bt = best_dice(hist[j, 0], hist[j, 1], summ["inv_bin"])
                         row.update(dice="" if counts is None else repr(dice_from_counts(counts[0][j], counts[1][j], counts[2][j])),
                                    best_dice=repr(bd), best_dice_threshold=repr(bt), average_precision=repr(average_precision(hist[j, 0], hist[j, 1])))
+                    if comp is not None:
+                        row.update(components=str(int(comp["components"][j])), components_kept=str(int(comp["components_kept"][j])),
+                                   voxels_kept=str(int(comp["voxels_kept"][j])), largest_component=str(int(comp["largest_component"][j])))
+                        if labels is not None:
+                            rc, pr, f1 = lesion_scores(comp["lesions"][j], comp["lesions_detected"][j], comp["components_kept"][j], comp["kept_true"][j])
+                            row.update(dice_cleaned=repr(dice_from_counts(comp["tp"][j], comp["fp"][j], comp["fn"][j])),
+                                       lesions=str(int(comp["lesions"][j])), lesions_detected=str(int(comp["lesions_detected"][j])),
+                                       lesion_recall=repr(rc), lesion_precision=repr(pr), lesion_f1=repr(f1))
                     if specs is not None:
                         row["members"] = str(summ["members"])
                     rows.append(row)
@@ -747,6 +791,9 @@ def anomaly(cfg, rank, local, world, dev):
         if saver is not None:
             saver.close()
     fields = ["subject", "sum", "max"] + (["dice", "best_dice", "best_dice_threshold", "average_precision"] if label_files is not None else [])
+    if min_component is not None:
+        fields += ["components", "components_kept", "voxels_kept", "largest_component"]
+        fields += ["dice_cleaned", "lesions", "lesions_detected", "lesion_recall", "lesion_precision", "lesion_f1"] if label_files is not None else []
     fields += ["members"] if specs is not None else []
     with open(os.path.join(cfg["outputs_directory"], f"anomaly_scores_rank{rank}.csv"), "w", newline="") as f:
         wr = csv.DictWriter(f, fieldnames=fields)
@@ -762,7 +809,8 @@ def run(argv):
         raise ValueError(f"VQVAE mode unknown. Was given {cfg['mode']} but choices are {MODES}.")
     _check_output_flags(cfg)
     _check_codebook_flags(cfg)
-    if cfg["mode"] == "anomaly" or cfg["anomaly_ensemble"] is not None:
+    if (cfg["mode"] == "anomaly" or cfg["anomaly_ensemble"] is not None or cfg["anomaly_min_component"] is not None
+            or cfg["anomaly_connectivity"] != DEFAULTS["anomaly_connectivity"]):
         _check_anomaly_flags(cfg)
     cfg["perceptual_state"] = _check_perceptual_flags(cfg) if cfg["mode"] == "training" else None
     rank, local, world = init_distributed()

@@ -83,6 +83,17 @@ class AnomalyParams(Structure):
                 ("R", c_int32), ("has_threshold", c_int32), ("inv_bin", c_float), ("threshold", c_float), ("taps", c_float * (2 * ANOMALY_MAX_R + 1))]
 
 
+# include/synthanatomy_hip.h: SA_COMPONENTS_TILE_D / H / W, SA_COMPONENTS_RESULT_WORDS.  One result record per volume, int64 words: [0] components,
+# [1] kept, [2] foreground voxels, [3] kept voxels, [4] largest, [5], [6], [7] TP, FP, FN, [8] lesions, [9] lesions detected, [10] kept with a class-1 voxel
+COMPONENTS_TILE, COMPONENTS_RESULT_WORDS = (8, 16, 16), 16
+
+
+class ComponentsParams(Structure):
+    """sa_components_params (include/synthanatomy_hip.h): read on the host by sa_components."""
+    _fields_ = [("B", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32), ("connectivity", c_int32), ("min_size", c_int32),
+                ("has_labels", c_int32), ("threshold", c_float)]
+
+
 _SIGS = {
     "sa_abi_version": (c_int, []),
     "sa_last_error": (c_char_p, []),
@@ -149,6 +160,8 @@ _SIGS = {
     "sa_anomaly_map_workspace_bytes": (c_int64, [POINTER(AnomalyParams)]),
     "sa_anomaly_map_ensemble": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(AnomalyParams), c_int, c_void_p,
                                         c_void_p, c_void_p]),
+    "sa_components": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(ComponentsParams), c_void_p, c_void_p, c_void_p]),
+    "sa_components_workspace_bytes": (c_int64, [POINTER(ComponentsParams)]),
     "sa_bn_sums_ws_floats": (c_int64, [c_int]),
     "sa_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "sa_embed_sum": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p]),
