@@ -405,6 +405,34 @@ typedef struct sa_components_params {
 int sa_components(const float *a, const unsigned char *label, int32_t *ids_out, const sa_components_params *params, void *results, void *ws,
                   void *stream);
 int64_t sa_components_workspace_bytes(const sa_components_params *params);
+/* Masked 3-D median filter of an anomaly map with the summaries of sa_anomaly_map (metrics/median.py, run_vqvae.py --anomaly_median / --anomaly_mask;
+ * csrc/median.hip; this project's own rule, no reference counterpart).  a [B, D, H, W] fp32 contiguous device tensor; mask (NULL iff
+ * has_mask == 0) and label (NULL iff has_labels == 0) [B, D, H, W] bytes: foreground / class 1 where != 0; out [B, D, H, W] fp32, which may not be a.
+ * params is read on the HOST.  Per volume:
+ *   m0 = [mask != 0] (1 everywhere without a mask);  m(v) = AND of m0(v + t) over |t|_1 <= erosion, false where v + t leaves the volume (erosion
+ *   steps with the 6-neighbourhood);  a'(v) = m(v) ? a(v) : +0.0f, a select;  f(v) = the element of rank (size^3 - 1) / 2 (0-based, ascending) among the
+ *   size^3 values a'(v + t), t in [-size/2, size/2]^3, +0.0f where v + t leaves the volume, ordered by the unsigned key
+ *   bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) of the fp32 bits (a total order: -0 < +0, negative NaNs below -inf, positive NaNs above +inf);
+ *   out(v) = m(v) ? f(v) : +0.0f, the bits of the chosen element.  size = 1 is the mask alone.
+ * results: B records of SA_ANOMALY_RESULT_WORDS words with sa_anomaly_map's meanings, taken over out (the call clears them first); a product
+ * out * inv_bin below zero counts in bin 0, a NaN in bin 255.  Float sums are added in a fixed order without float atomics; out and the record of a
+ * volume are bitwise the same alone, in any batch and from call to call.  A clear, `erosion` erosion steps, the filter with its summaries and the
+ * per-volume sums on the stream, no host synchronisation.  ws: sa_anomaly_median_workspace_bytes(params) bytes, 16-byte aligned; results 8-byte aligned.
+ * SA_EINVAL (nothing launched) for null a / out / results / ws / params, a dim < 1, size outside {1, 3, 5}, erosion outside 0..4, erosion > 0 without a
+ * mask, a mask or label pointer that disagrees with its has_* flag, inv_bin not positive and finite, a non-finite threshold with has_threshold,
+ * out == a; SA_EUNSUPPORTED for B > 65535 and D H W >= 2^31 - 1. */
+enum { SA_MEDIAN_TILE_D = 8, SA_MEDIAN_TILE_H = 16, SA_MEDIAN_TILE_W = 32, SA_MEDIAN_MAX_EROSION = 4 };
+typedef struct sa_median_params {
+    int32_t B, D, H, W;
+    int32_t size;               /* 1 | 3 | 5: the window's side */
+    int32_t erosion;            /* 0 .. SA_MEDIAN_MAX_EROSION */
+    int32_t has_mask, has_labels, has_threshold;
+    float inv_bin;              /* 256 / hist_max */
+    float threshold;
+} sa_median_params; /* 44 bytes */
+int sa_anomaly_median(const float *a, const unsigned char *mask, const unsigned char *label, float *out, const sa_median_params *params,
+                      void *results, void *ws, void *stream);
+int64_t sa_anomaly_median_workspace_bytes(const sa_median_params *params);
 /* Adam (torch.optim.Adam semantics, run_vqvae.py:82-86) over a flat fp32 parameter buffer; step >= 1 */
 int sa_adam(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
             float weight_decay, int step, float grad_scale, void *stream);

@@ -65,6 +65,16 @@ as ``<name>_anomaly_map`` in one pass, with the scores of that mean; ``<name>_he
 below that many voxels and counts lesions; the single map and the ensemble map both go through it.  ``<name>_anomaly_segmentation`` ({0, 1}) is
 written like the map and the CSV gains ``components``, ``components_kept``, ``voxels_kept``, ``largest_component`` and, with ``--anomaly_labels``,
 ``dice_cleaned``, ``lesions``, ``lesions_detected``, ``lesion_recall``, ``lesion_precision``, ``lesion_f1`` (before ``members``).
+
+``--anomaly_median=1|3|5`` and ``--anomaly_mask=scan|<dir|glob>`` (MI355X-only; default None: nothing changes) filter the map, single or
+ensemble, on the device before the components: ``sa_anomaly_median`` restricts it to the mask by a select, takes the 3-D median of that side (zeros
+outside the volume) and restricts it again; a mask alone means side 1.  ``scan`` is ``[x > --anomaly_mask_threshold]`` (default 0.0, only valid with
+``scan``) of the scan as the encoder saw it; otherwise mask volumes are matched to the subjects by stem and loaded like ``--anomaly_labels``
+(reoriented and cropped like the scan, never normalised; foreground where > 0.5).  ``--anomaly_mask_erosion=0..4`` (default 0, needs a mask) erodes the
+mask that many times with the 6-neighbourhood, the outside of the volume counting as background.  ``<name>_anomaly_map`` stays the raw map,
+``<name>_anomaly_map_filtered`` is written like it, ``--anomaly_min_component`` then cleans the filtered map, and the CSV keeps its columns (the raw
+map's) and gains ``filtered_sum``, ``filtered_max`` and, with ``--anomaly_labels``, ``filtered_dice``, ``filtered_best_dice``,
+``filtered_best_dice_threshold``, ``filtered_average_precision`` before the component columns.
 """
 import os
 import sys
@@ -93,6 +103,7 @@ DEFAULTS = dict(
     codebook_restart_patience=None, codebook_restart_max=32,
     anomaly_codes=None, anomaly_weight="mask", anomaly_sigma=None, anomaly_residual="abs", anomaly_threshold=None, anomaly_hist_max=1.0, anomaly_labels=None,
     anomaly_ensemble=None, anomaly_min_component=None, anomaly_connectivity=26,
+    anomaly_median=None, anomaly_mask=None, anomaly_mask_threshold=0.0, anomaly_mask_erosion=0,
 )
 MODES = ["training", "extracting", "decoding", "anomaly"]
 
@@ -564,6 +575,7 @@ def _check_anomaly_flags(cfg):
     """the --anomaly_* flags act or refuse (before anything touches the device)"""
     from synthanatomy_amd.metrics.anomaly import MAX_MEMBERS, MAX_SIGMA, RESIDUALS
     from synthanatomy_amd.metrics.components import CONNECTIVITIES
+    _check_median_flags(cfg)
     for name, given in (("anomaly_min_component", cfg["anomaly_min_component"] is not None),
                         ("anomaly_connectivity", cfg["anomaly_connectivity"] != DEFAULTS["anomaly_connectivity"])):
         if not given:
@@ -615,6 +627,37 @@ def _check_anomaly_flags(cfg):
         raise ValueError(f"--no_augmented_extractions={cfg['no_augmented_extractions']}: --mode=anomaly compares every scan with its own healed codes")
 
 
+MEDIAN_FLAGS = ("anomaly_median", "anomaly_mask", "anomaly_mask_threshold", "anomaly_mask_erosion")
+
+
+def _median_flags_given(cfg):
+    return [name for name in MEDIAN_FLAGS if cfg[name] is not None and (isinstance(cfg[name], bool) or cfg[name] != DEFAULTS[name])]
+
+
+def _check_median_flags(cfg):
+    """--anomaly_median / --anomaly_mask / --anomaly_mask_threshold / --anomaly_mask_erosion act or refuse, each by its name"""
+    from synthanatomy_amd.metrics.median import MAX_EROSION, SIZES
+    for name in _median_flags_given(cfg):
+        if cfg["mode"] != "anomaly":
+            raise ValueError(f"--{name}={cfg[name]}: the flag belongs to --mode=anomaly, not --mode={cfg['mode']}")
+    k = cfg["anomaly_median"]
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k not in SIZES):
+        raise ValueError(f"--anomaly_median={k}: choices are 1, 3 and 5 (the window's side) or None")
+    mask = cfg["anomaly_mask"]
+    if mask is not None and (not isinstance(mask, str) or not mask.strip()):
+        raise ValueError(f"--anomaly_mask={mask}: scan, a directory or a glob is needed")
+    mt = cfg["anomaly_mask_threshold"]
+    if isinstance(mt, bool) or not isinstance(mt, (int, float)) or mt != mt or abs(mt) == float("inf"):
+        raise ValueError(f"--anomaly_mask_threshold={mt}: a finite number is needed")
+    if mt != DEFAULTS["anomaly_mask_threshold"] and mask != "scan":
+        raise ValueError(f"--anomaly_mask_threshold={mt}: the flag thresholds the scan and needs --anomaly_mask=scan (given: {mask})")
+    e = cfg["anomaly_mask_erosion"]
+    if isinstance(e, bool) or not isinstance(e, int) or not 0 <= e <= MAX_EROSION:
+        raise ValueError(f"--anomaly_mask_erosion={e}: an integer in 0..{MAX_EROSION} is needed")
+    if e > 0 and mask is None:
+        raise ValueError(f"--anomaly_mask_erosion={e}: there is nothing to erode without --anomaly_mask")
+
+
 def find_healing_outputs(subjects, spec, weight="mask"):
     """For every subject the files ``run_transformer.save_healing`` wrote for its codes, found by stem under ``spec`` (a directory, searched recursively,
     or a glob): ``<stem>_quantization_0_healed_sample.npy`` and next to it ``..._resampled.npy`` / ``..._nll.npy`` (``weight`` = mask / nll says which
@@ -664,14 +707,15 @@ def find_ensemble_outputs(subjects, specs, weight="mask"):
     return members
 
 
-def match_labels(subjects, spec):
-    """the label volume of every subject, matched by stem among ``list_inputs(spec)``; a subject without exactly one is refused by name"""
+def match_labels(subjects, spec, flag="anomaly_labels", what="label"):
+    """the label volume of every subject, matched by stem among ``list_inputs(spec)``; a subject without exactly one is refused by name
+    (``--anomaly_mask=<dir|glob>`` finds its mask volumes the same way)"""
     found = list_inputs(spec)
     out = []
     for s in subjects:
         hits = [f for f in found if _stem(f) == _stem(s)]
         if len(hits) != 1:
-            raise ValueError(f"{s}: {len(hits)} label volumes with the stem {_stem(s)} in --anomaly_labels={spec} (exactly one is needed)")
+            raise ValueError(f"{s}: {len(hits)} {what} volumes with the stem {_stem(s)} in --{flag}={spec} (exactly one is needed)")
         out.append(hits[0])
     return out
 
@@ -681,7 +725,9 @@ def anomaly(cfg, rank, local, world, dev):
     import csv
     from synthanatomy_amd.metrics.anomaly import anomaly_map, anomaly_map_ensemble, average_precision, best_dice, dice_from_counts
     from synthanatomy_amd.metrics.components import connected_components, lesion_scores
+    from synthanatomy_amd.metrics.median import median_filter_map
     min_component = cfg["anomaly_min_component"]
+    filtered = cfg["anomaly_median"] is not None or cfg["anomaly_mask"] is not None      # DESIGN 7.18; a mask alone is size 1
     files = list_inputs(cfg["validation_subjects"])
     specs = _ensemble_specs(cfg)      # K healings per subject, one fused map; None: the single healing of 7.11
     if specs is None:
@@ -689,6 +735,9 @@ def anomaly(cfg, rank, local, world, dev):
     else:
         members = find_ensemble_outputs(files, specs, cfg["anomaly_weight"])
     label_files = match_labels(files, cfg["anomaly_labels"]) if cfg["anomaly_labels"] is not None else None
+    mask_files = None
+    if cfg["anomaly_mask"] not in (None, "scan"):
+        mask_files = match_labels(files, cfg["anomaly_mask"], "anomaly_mask", "mask")
     sigma = _anomaly_sigma(cfg)
     net = build_network(cfg, dev).eval()
     path = check_for_checkpoints(cfg)
@@ -742,17 +791,29 @@ def anomaly(cfg, rank, local, world, dev):
                     amap, summ = anomaly_map_ensemble(x, block, torch.stack(wgts) if wgts[0] is not None else None, sigma=sigma,
                                                       residual=cfg["anomaly_residual"], labels=labels, threshold=cfg["anomaly_threshold"],
                                                       hist_max=cfg["anomaly_hist_max"])
+                fmap = fsumm = None
+                if filtered:      # mask, median, mask again on the device; the components below take the filtered map
+                    mask = None
+                    if cfg["anomaly_mask"] == "scan":
+                        mask = x > float(cfg["anomaly_mask_threshold"])
+                    elif mask_files is not None:
+                        mask = torch.stack([_load_volume(mask_files[index[n]], raw_cfg, gen, dev).reshape(x.shape[1:]) for n in names])
+                    fmap, fsumm = median_filter_map(amap, size=cfg["anomaly_median"] or 1, mask=mask, erosion=cfg["anomaly_mask_erosion"], labels=labels,
+                                                    threshold=cfg["anomaly_threshold"], hist_max=cfg["anomaly_hist_max"])
                 seg = comp = None
                 if min_component is not None:      # the map, single or ensemble, is still on the device
-                    ids, comp = connected_components(amap, threshold=cfg["anomaly_threshold"], connectivity=int(cfg["anomaly_connectivity"]),
+                    ids, comp = connected_components(fmap if filtered else amap, threshold=cfg["anomaly_threshold"], connectivity=int(cfg["anomaly_connectivity"]),
                                                      min_size=min_component, labels=labels)
                     seg = (ids > 0).float()
                 posts = ["healed_reconstruction"] if specs is None else [f"healed_reconstruction_m{k}" for k in range(len(members))]
                 if saver is None:
                     host = [rec.cpu().numpy() for rec in recs]
                     seg_host = seg.cpu().numpy() if seg is not None else None
+                    f_host = fmap.cpu().numpy() if filtered else None
                     for j, (n, a_) in enumerate(zip(names, amap.cpu().numpy())):
                         save_npy(a_[0], cfg["outputs_directory"], n, "anomaly_map", np.float32)
+                        if filtered:
+                            save_npy(f_host[j, 0], cfg["outputs_directory"], n, "anomaly_map_filtered", np.float32)
                         if seg_host is not None:
                             save_npy(seg_host[j, 0], cfg["outputs_directory"], n, "anomaly_segmentation", np.float32)
                         for post, r_ in zip(posts, host):
@@ -762,6 +823,8 @@ def anomaly(cfg, rank, local, world, dev):
                     for j, (n, a_, h) in enumerate(zip(names, amap, headers)):
                         geom = nifti_output_geometry(h, cfg["roi"], canonical, a_.shape[-3:])
                         saver.save(a_[0], _output_path(cfg, n, "anomaly_map"), *geom)
+                        if filtered:
+                            saver.save(fmap[j, 0], _output_path(cfg, n, "anomaly_map_filtered"), *geom)
                         if seg is not None:
                             saver.save(seg[j, 0], _output_path(cfg, n, "anomaly_segmentation"), *geom)
                         for post, rec in zip(posts, recs):
@@ -770,12 +833,22 @@ def anomaly(cfg, rank, local, world, dev):
                     comp = {k: v.cpu().numpy() for k, v in comp.items() if v is not None}
                 sums, maxs, hist = summ["sum"].cpu().numpy(), summ["max"].cpu().numpy(), summ["hist"].cpu().numpy()
                 counts = [summ[k].cpu().numpy() for k in ("tp", "fp", "fn")] if summ["tp"] is not None else None
+                if filtered:
+                    fsums, fmaxs, fhist = fsumm["sum"].cpu().numpy(), fsumm["max"].cpu().numpy(), fsumm["hist"].cpu().numpy()
+                    fcounts = [fsumm[k].cpu().numpy() for k in ("tp", "fp", "fn")] if fsumm["tp"] is not None else None
                 for j, n in enumerate(names):
                     row = {"subject": _stem(n), "sum": repr(float(sums[j])), "max": repr(float(maxs[j]))}
                     if labels is not None:
                         bd, bt = best_dice(hist[j, 0], hist[j, 1], summ["inv_bin"])
                         row.update(dice="" if counts is None else repr(dice_from_counts(counts[0][j], counts[1][j], counts[2][j])),
                                    best_dice=repr(bd), best_dice_threshold=repr(bt), average_precision=repr(average_precision(hist[j, 0], hist[j, 1])))
+                    if filtered:
+                        row.update(filtered_sum=repr(float(fsums[j])), filtered_max=repr(float(fmaxs[j])))
+                        if labels is not None:
+                            bd, bt = best_dice(fhist[j, 0], fhist[j, 1], fsumm["inv_bin"])
+                            row.update(filtered_dice="" if fcounts is None else repr(dice_from_counts(fcounts[0][j], fcounts[1][j], fcounts[2][j])),
+                                       filtered_best_dice=repr(bd), filtered_best_dice_threshold=repr(bt),
+                                       filtered_average_precision=repr(average_precision(fhist[j, 0], fhist[j, 1])))
                     if comp is not None:
                         row.update(components=str(int(comp["components"][j])), components_kept=str(int(comp["components_kept"][j])),
                                    voxels_kept=str(int(comp["voxels_kept"][j])), largest_component=str(int(comp["largest_component"][j])))
@@ -791,6 +864,9 @@ def anomaly(cfg, rank, local, world, dev):
         if saver is not None:
             saver.close()
     fields = ["subject", "sum", "max"] + (["dice", "best_dice", "best_dice_threshold", "average_precision"] if label_files is not None else [])
+    if filtered:
+        fields += ["filtered_sum", "filtered_max"]
+        fields += ["filtered_dice", "filtered_best_dice", "filtered_best_dice_threshold", "filtered_average_precision"] if label_files is not None else []
     if min_component is not None:
         fields += ["components", "components_kept", "voxels_kept", "largest_component"]
         fields += ["dice_cleaned", "lesions", "lesions_detected", "lesion_recall", "lesion_precision", "lesion_f1"] if label_files is not None else []
@@ -810,7 +886,7 @@ def run(argv):
     _check_output_flags(cfg)
     _check_codebook_flags(cfg)
     if (cfg["mode"] == "anomaly" or cfg["anomaly_ensemble"] is not None or cfg["anomaly_min_component"] is not None
-            or cfg["anomaly_connectivity"] != DEFAULTS["anomaly_connectivity"]):
+            or cfg["anomaly_connectivity"] != DEFAULTS["anomaly_connectivity"] or _median_flags_given(cfg)):
         _check_anomaly_flags(cfg)
     cfg["perceptual_state"] = _check_perceptual_flags(cfg) if cfg["mode"] == "training" else None
     rank, local, world = init_distributed()

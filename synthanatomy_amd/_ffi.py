@@ -94,6 +94,16 @@ class ComponentsParams(Structure):
                 ("has_labels", c_int32), ("threshold", c_float)]
 
 
+# include/synthanatomy_hip.h: SA_MEDIAN_TILE_D / H / W, the block's output tile of sa_anomaly_median; its records are ANOMALY_RESULT_WORDS long
+MEDIAN_TILE, MEDIAN_MAX_EROSION = (8, 16, 32), 4
+
+
+class MedianParams(Structure):
+    """sa_median_params (include/synthanatomy_hip.h): read on the host by sa_anomaly_median."""
+    _fields_ = [("B", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32), ("size", c_int32), ("erosion", c_int32), ("has_mask", c_int32),
+                ("has_labels", c_int32), ("has_threshold", c_int32), ("inv_bin", c_float), ("threshold", c_float)]
+
+
 _SIGS = {
     "sa_abi_version": (c_int, []),
     "sa_last_error": (c_char_p, []),
@@ -162,6 +172,8 @@ _SIGS = {
                                         c_void_p, c_void_p]),
     "sa_components": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(ComponentsParams), c_void_p, c_void_p, c_void_p]),
     "sa_components_workspace_bytes": (c_int64, [POINTER(ComponentsParams)]),
+    "sa_anomaly_median": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(MedianParams), c_void_p, c_void_p, c_void_p]),
+    "sa_anomaly_median_workspace_bytes": (c_int64, [POINTER(MedianParams)]),
     "sa_bn_sums_ws_floats": (c_int64, [c_int]),
     "sa_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "sa_embed_sum": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p]),

@@ -35,6 +35,8 @@ def _digest(path):
         hdrs = [h for h in hdrs if not h.endswith(("conv_fprop_common.h", "conv_fprop_kernels.h"))]     # only the forward translation units depend on them
     if not path.endswith(("local_attn.hip", "favor_fused.hip")):
         hdrs = [h for h in hdrs if not h.endswith("local_attn_split.h")]
+    if not path.endswith(("anomaly.hip", "median.hip")):
+        hdrs = [h for h in hdrs if not h.endswith("anomaly_summary.h")]
     for dep in [path, *hdrs, os.path.join(HERE, "..", "include", "synthanatomy_hip.h")]:
         with open(dep, "rb") as f:
             h.update(f.read())

@@ -24,16 +24,14 @@
 // the three band tables, the histogram clear and the summary epilogue happen once; per member the thread's 16 r_k values (requested before that
 // member's plane walk and used after it, as the single map's are), the walk over m_k's latent planes through the same ms / T1 buffers, and s = s + e_k w_k in member order
 // (s = a_0 for the first).  The map is a = s inv_K, one fp32 multiply; the summaries are taken over a.  K and every loop bound are uniform over the block.
-#include "sa_common.h"
+#include "anomaly_summary.h"
 
 namespace sa {
 
 constexpr int AN_TW = 32, AN_TH = 8, AN_LD = 16;      // tile: W x H voxels (one column per thread), planes per run (16: 61 us against 79 for 8 on a
                                                       // 160 x 224 x 160 volume, same call; 32 would leave 700 blocks for 256 CUs)
-constexpr int AN_THREADS = AN_TW * AN_TH;
+static_assert(AN_TW * AN_TH == AN_THREADS, "one (h, w) column per thread of the summary's block (anomaly_summary.h)");
 constexpr int AN_TAPS = 2 * SA_ANOMALY_MAX_R + 1;
-constexpr int AN_WORDS = SA_ANOMALY_RESULT_WORDS;
-constexpr int AN_PART = 8;                           // 64-bit words a block leaves in the workspace
 
 struct AnGeom {
     int D, H, W, d, h, w, fD, fH, fW, R;
@@ -55,23 +53,7 @@ static int64_t an_align(int64_t v) { return (v + 15) & ~(int64_t)15; }
 static int64_t an_lds_floats(const AnGeom& g) {
     return 64 + (int64_t)g.nDm * AN_LD + (int64_t)g.nHm * AN_TH + (int64_t)g.nWm * AN_TW + (int64_t)g.nHm * g.nWm + (int64_t)g.nHm * AN_TW;
 }
-static int64_t an_lds_bytes(const AnGeom& g) { return an_align(an_lds_floats(g) * 4) + 512 * 4 + 4 * 8 + 4 * 4 + 20 * 4; }
-
-__device__ __forceinline__ double an_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float an_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t an_wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+static int64_t an_lds_bytes(const AnGeom& g) { return an_align(an_lds_floats(g) * 4) + AN_TAIL_BYTES; }
 
 // A[p][c]: the taps of voxel p's window that fall into cell c, added in ascending order (at most min(f, 2R + 1) of them)
 __device__ __forceinline__ float an_band(const float* gs, int R, int p, int c, int f) {
@@ -102,10 +84,8 @@ __device__ __forceinline__ void anomaly_map_body(const float* __restrict__ x, co
     float* T1 = ms + g.nHm * g.nWm;
     const int64_t nfl = 64 + (int64_t)g.nDm * AN_LD + (int64_t)g.nHm * AN_TH + (int64_t)g.nWm * AN_TW + (int64_t)g.nHm * g.nWm + (int64_t)g.nHm * AN_TW;
     char* tail = an_smem + ((nfl * 4 + 15) & ~(int64_t)15);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(tail);               // [2][256]
-    double* red_s = reinterpret_cast<double*>(tail + 512 * 4);         // [4]
-    float* red_m = reinterpret_cast<float*>(tail + 512 * 4 + 4 * 8);   // [4]
-    uint32_t* red_c = reinterpret_cast<uint32_t*>(tail + 512 * 4 + 4 * 8 + 4 * 4);      // [5][4]
+    const AnTail T = an_tail(tail);      // the summary's histogram and wave slots (anomaly_summary.h)
+    uint32_t* hist = T.hist;
 
     const int tid = threadIdx.x, wl = tid % AN_TW, hl = tid / AN_TW;
     const int64_t b = blockIdx.y;
@@ -210,9 +190,7 @@ __device__ __forceinline__ void anomaly_map_body(const float* __restrict__ x, co
         }
     }
 
-    double bs = 0.0;
-    float bm = 0.f;
-    uint32_t cnt[5] = {0u, 0u, 0u, 0u, 0u};      // bin 0 of class 0, bin 0 of class 1, TP, FP, FN
+    AnAcc acc;
 #pragma unroll
     for (int k = 0; k < AN_LD; ++k) {
         if (valid && k < np) {
@@ -220,48 +198,10 @@ __device__ __forceinline__ void anomaly_map_body(const float* __restrict__ x, co
             const float e = g.mode == SA_ANOMALY_ABS ? fabsf(dlt) : g.mode == SA_ANOMALY_POSITIVE ? fmaxf(dlt, 0.f) : fmaxf(-dlt, 0.f);
             const float a = ENS ? sacc[k] * M.inv_K : m ? e * wacc[k] : e;
             a_out[base + k * plane] = a;
-            bs += (double)a;
-            bm = fmaxf(bm, a);
-            const int bin = (int)fminf(a * g.inv_bin, 255.f);
-            const uint32_t cls = lv[k] != 0 ? 1u : 0u;
-            if (bin == 0) {
-                cnt[0] += cls ^ 1u;
-                cnt[1] += cls;
-            } else {
-                atomicAdd(&hist[cls * 256u + (uint32_t)bin], 1u);
-            }
-            if (g.has_t) {
-                const uint32_t pred = a >= g.t ? 1u : 0u;
-                cnt[2] += pred & cls;
-                cnt[3] += pred & (cls ^ 1u);
-                cnt[4] += (pred ^ 1u) & cls;
-            }
+            an_account(acc, hist, a, lv[k] != 0 ? 1u : 0u, g.inv_bin, g.has_t != 0, g.t);
         }
     }
-    bs = an_wave_sum_f64(bs);
-    bm = an_wave_max(bm);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) cnt[q] = an_wave_sum_u32(cnt[q]);
-    unsigned long long* res = results + b * AN_WORDS;
-    if ((tid & 63) == 0) {
-        red_s[tid >> 6] = bs;
-        red_m[tid >> 6] = bm;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) red_c[q * 4 + (tid >> 6)] = cnt[q];
-    }
-    __syncthreads();
-    unsigned long long* pp = part + (b * g.nblk + blockIdx.x) * AN_PART;
-    if (tid == 0) {
-        pp[0] = (unsigned long long)__double_as_longlong((red_s[0] + red_s[1]) + (red_s[2] + red_s[3]));
-        pp[1] = (unsigned long long)__double_as_longlong((double)fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3])));
-    } else if (tid < 6) {
-        const uint32_t* c = red_c + (tid - 1) * 4;
-        pp[1 + tid] = (unsigned long long)c[0] + c[1] + c[2] + c[3];
-    }
-    for (int i = tid; i < 512; i += AN_THREADS) {      // (words 0 and 256 stay empty here: bin 0 travels through the workspace)
-        const uint32_t v = hist[i];
-        if (v) atomicAdd(res + 8 + i, (unsigned long long)v);
-    }
+    an_block_finish(acc, T, part + (b * g.nblk + blockIdx.x) * AN_PART, results + b * AN_WORDS);
 }
 
 __global__ __launch_bounds__(AN_THREADS) void anomaly_map_kernel(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ m,
@@ -279,45 +219,9 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_map_ensemble_kernel(const 
     anomaly_map_body<true>(x, r, m, label, a_out, g, taps, part, results, M);
 }
 
-// results[b][0] = sum a, [1] = max a (both as doubles), [2..4] = TP, FP, FN, [8] and [8 + 256] = bin 0 of the two classes: one block per volume, lanes
-// and waves in a fixed order
+// one block per volume adds the blocks' partial words in a fixed order (an_finish_body, anomaly_summary.h)
 __global__ __launch_bounds__(256) void anomaly_finish_kernel(const unsigned long long* __restrict__ part, int nblk, unsigned long long* __restrict__ results) {
-    __shared__ double red_s[4], red_m[4];
-    __shared__ unsigned long long red_c[5][4];
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const unsigned long long* pp = part + b * nblk * AN_PART;
-    double s = 0.0, mx = 0.0;
-    unsigned long long c[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-    for (int i = tid; i < nblk; i += 256) {
-        s += __longlong_as_double((long long)pp[AN_PART * i]);
-        mx = fmax(mx, __longlong_as_double((long long)pp[AN_PART * i + 1]));
-#pragma unroll
-        for (int q = 0; q < 5; ++q) c[q] += pp[AN_PART * i + 2 + q];
-    }
-    s = an_wave_sum_f64(s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
-#pragma unroll
-        for (int q = 0; q < 5; ++q) c[q] += __shfl_xor(c[q], o, 64);
-    }
-    if ((tid & 63) == 0) {
-        red_s[tid >> 6] = s;
-        red_m[tid >> 6] = mx;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) red_c[q][tid >> 6] = c[q];
-    }
-    __syncthreads();
-    unsigned long long* res = results + b * AN_WORDS;
-    if (tid == 0) {
-        res[0] = (unsigned long long)__double_as_longlong((red_s[0] + red_s[1]) + (red_s[2] + red_s[3]));
-        res[1] = (unsigned long long)__double_as_longlong(fmax(fmax(red_m[0], red_m[1]), fmax(red_m[2], red_m[3])));
-    } else if (tid < 6) {
-        const int q = tid - 1;
-        const unsigned long long v = red_c[q][0] + red_c[q][1] + red_c[q][2] + red_c[q][3];
-        res[q == 0 ? 8 : q == 1 ? 8 + 256 : q] = v;      // q = 2, 3, 4: TP, FP, FN sit in words 2, 3, 4
-    }
+    an_finish_body(part, nblk, results);
 }
 
 }  // namespace sa

@@ -1,0 +1,342 @@
+"""CPU: the masked median rule of DESIGN §7.18 -- the numpy reference against scipy and against a voxel-by-voxel loop, the key order, two witnesses that
+the tests have teeth, every refusal of ``metrics/median.py`` and of the ``--anomaly_median`` / ``--anomaly_mask*`` flags with no device, and the ABI."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import median_ref as ref
+import run_vqvae as RV
+from synthanatomy_amd.metrics import median as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RAGGED = [(5, 5, 5), (2, 3, 5), (1, 1, 70), (9, 17, 33), (13, 6, 11)]
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float32).view(np.int32)
+
+
+# ---- the reference ----
+
+def test_the_key_order_is_strict_and_round_trips_the_bits():
+    neg_nan = np.array([0xFFC00000], dtype=np.uint32).view(np.float32)[0]
+    pos_nan = np.array([0x7FC00000], dtype=np.uint32).view(np.float32)[0]
+    x = np.array([neg_nan, -np.inf, -1.0, -0.0, 0.0, 1.0, np.inf, pos_nan], dtype=np.float32)
+    key = ref.to_key(x)
+    assert key.dtype == np.uint32 and np.all(key[1:] > key[:-1])
+    assert key[4] == ref.ZERO_KEY and key[3] == ref.ZERO_KEY - 1
+    assert _bits(ref.from_key(key)).tobytes() == _bits(x).tobytes()
+    every = np.random.default_rng(0).integers(0, 2 ** 32, 4096, dtype=np.uint64).astype(np.uint32)
+    assert np.array_equal(ref.to_key(ref.from_key(every)), every)
+
+
+@pytest.mark.parametrize("shape", RAGGED)
+def test_the_reference_equals_scipy_on_finite_inputs(shape):
+    ndi = pytest.importorskip("scipy.ndimage", reason="scipy is not installed: the reference is still held to the voxel loop")
+    rng = np.random.default_rng(sum(shape))
+    a = rng.standard_normal(shape).astype(np.float32)
+    a[a == 0] = 1.0      # no signed zeros: scipy's order does not tell them apart
+    m0 = rng.random(shape) < 0.9
+    for e in range(5):
+        want = ndi.binary_erosion(m0, iterations=e, border_value=0) if e else m0
+        assert np.array_equal(ref.erode(m0, e), want)
+    for k in (1, 3, 5):
+        assert np.array_equal(ref.median(a, k), ndi.median_filter(a, size=k, mode="constant", cval=0.0))
+        m = ref.erode(m0, 1)
+        sel = np.where(m, a, np.float32(0))
+        assert np.array_equal(ref.median(a, k, m0.astype(np.uint8), 1), np.where(m, ndi.median_filter(sel, size=k, mode="constant", cval=0.0), np.float32(0)))
+
+
+def _loop(a, k, mask, e):
+    """the rule, voxel by voxel"""
+    D, H, W = a.shape
+    r = k // 2
+
+    def inside(d, h, w):
+        return 0 <= d < D and 0 <= h < H and 0 <= w < W
+
+    def m(d, h, w):
+        if mask is None:
+            return True
+        return all(inside(d + i, h + j, w + l) and mask[d + i, h + j, w + l] != 0
+                   for i in range(-e, e + 1) for j in range(-e, e + 1) for l in range(-e, e + 1) if abs(i) + abs(j) + abs(l) <= e)
+    out = np.zeros(a.shape, dtype=np.float32)
+    for d in range(D):
+        for h in range(H):
+            for w in range(W):
+                if not m(d, h, w):
+                    continue
+                window = []
+                for i in range(-r, r + 1):
+                    for j in range(-r, r + 1):
+                        for l in range(-r, r + 1):
+                            q = (d + i, h + j, w + l)
+                            window.append(a[q] if inside(*q) and m(*q) else np.float32(0.0))
+                keys = np.sort(ref.to_key(np.array(window, dtype=np.float32)), kind="stable")
+                out[d, h, w] = ref.from_key(keys[(k ** 3 - 1) // 2:(k ** 3 - 1) // 2 + 1])[0]
+    return out
+
+
+@pytest.mark.parametrize("shape", [(5, 5, 8), (2, 3, 5), (1, 1, 40), (7, 4, 7), (6, 6, 5)])
+def test_the_reference_equals_a_voxel_by_voxel_loop(shape):
+    assert np.prod(shape) <= 200
+    rng = np.random.default_rng(shape[0])
+    a = rng.standard_normal(shape).astype(np.float32)
+    a[rng.random(shape) < 0.1] = np.float32(np.nan)
+    a[rng.random(shape) < 0.1] = np.float32(-0.0)
+    a[rng.random(shape) < 0.05] = np.float32(-np.inf)
+    mask = (rng.random(shape) < 0.92).astype(np.uint8) * 200
+    for k, mk, e in ((1, None, 0), (3, None, 0), (5, None, 0), (3, mask, 0), (5, mask, 1), (3, mask, 2), (1, mask, 1)):
+        assert _bits(ref.median(a, k, mk, e)).tobytes() == _bits(_loop(a, k, mk, e)).tobytes(), (k, e)
+
+
+def test_reflecting_the_border_instead_of_zero_padding_differs():
+    ndi = pytest.importorskip("scipy.ndimage", reason="scipy is not installed")
+    a = np.ones((5, 5, 5), dtype=np.float32)      # a corner window holds 27 ones and 98 padded zeros under the rule
+    assert ref.median(a, 5)[0, 0, 0] == 0.0 and ndi.median_filter(a, size=5, mode="reflect")[0, 0, 0] == 1.0
+    assert ref.median(a, 5)[2, 2, 2] == 1.0
+
+
+def test_the_padding_is_zero_without_scipy_too():
+    a = np.ones((5, 5, 5), dtype=np.float32)
+    out = ref.median(a, 5)
+    assert out[0, 0, 0] == 0.0 and out[2, 2, 2] == 1.0 and out[0, 2, 2] == 1.0 and out[0, 0, 2] == 0.0      # 27, 125, 75 and 45 of 125 inside; rank 62
+    assert ref.median(a, 3)[0, 1, 1] == 1.0 and ref.median(a, 3)[0, 0, 1] == 0.0      # 18 of 27 inside; 12 of 27 inside
+
+
+def test_multiplying_by_the_mask_instead_of_selecting_differs():
+    mask = np.ones((3, 3, 3), dtype=np.uint8)
+    mask[0, 0, 0] = 0
+    for outside in (np.float32(np.nan), np.float32(-2.0)):
+        a = np.full((3, 3, 3), 1.0, dtype=np.float32)
+        a[0, 0, 0] = outside
+        got = ref.median(a, 1, mask)
+        with np.errstate(invalid="ignore"):
+            product = a * mask.astype(np.float32)
+        assert _bits(got)[0, 0, 0] == 0 and _bits(product)[0, 0, 0] != 0      # NaN * 0 is NaN, -2 * 0 is -0
+        # and the -0 of the product is another element of the order than the +0 of the select
+        assert ref.to_key(product[:1, 0, 0])[0] != ref.ZERO_KEY
+
+
+def test_summaries_on_a_hand_made_volume():
+    out = np.array([[[0.0, 0.1, 0.5, 3.0]]], dtype=np.float32)
+    y = np.array([[[0, 1, 1, 0]]], dtype=np.uint8)
+    s = ref.summaries(out, np.float32(256.0), y, 0.5)
+    assert s["hist"][0, 0] == 1 and s["hist"][1, 25] == 1 and s["hist"][1, 128] == 1 and s["hist"][0, 255] == 1 and s["hist"].sum() == 4
+    assert (s["tp"], s["fp"], s["fn"]) == (1, 1, 1) and s["max"] == np.float32(3.0) and s["sum"] == float(out.astype(np.float64).sum())
+    assert ref.summaries(out, np.float32(256.0))["tp"] is None
+
+
+# ---- refusals, no device ----
+
+def test_check_arguments_accepts_and_returns_what_the_kernel_gets():
+    assert M.check_arguments((2, 1, 3, 4, 5), 5, None, 0, None, None, 1.0) == ((2, 3, 4, 5), 5, 0, None, np.float32(256.0))
+    got = M.check_arguments((2, 3, 4, 5), np.int64(3), (2, 3, 4, 5), 4, (2, 3, 4, 5), 0.5, 0.25)
+    assert got == ((2, 3, 4, 5), 3, 4, 0.5, np.float32(1024.0))
+    assert M.SIZES == (1, 3, 5) and M.MAX_EROSION == 4
+
+
+@pytest.mark.parametrize("args, match", [
+    (((2, 3, 4), 5, None, 0, None, None, 1.0), "volumes"),
+    (((2, 2, 3, 4, 5), 5, None, 0, None, None, 1.0), "volumes"),
+    (((2, 0, 4, 5), 5, None, 0, None, None, 1.0), "every side"),
+    (((65536, 1, 1, 1), 5, None, 0, None, None, 1.0), "65535"),
+    (((1, 1 << 11, 1 << 10, 1 << 10), 5, None, 0, None, None, 1.0), r"2\^31 - 1"),
+    (((2, 3, 4, 5), 2, None, 0, None, None, 1.0), "size"),
+    (((2, 3, 4, 5), 7, None, 0, None, None, 1.0), "size"),
+    (((2, 3, 4, 5), 3.0, None, 0, None, None, 1.0), "size"),
+    (((2, 3, 4, 5), True, None, 0, None, None, 1.0), "size"),
+    (((2, 3, 4, 5), "5", None, 0, None, None, 1.0), "size"),
+    (((2, 3, 4, 5), 5, (2, 3, 4, 5), 5, None, None, 1.0), "erosion"),
+    (((2, 3, 4, 5), 5, (2, 3, 4, 5), -1, None, None, 1.0), "erosion"),
+    (((2, 3, 4, 5), 5, (2, 3, 4, 5), 1.0, None, None, 1.0), "erosion"),
+    (((2, 3, 4, 5), 5, (2, 3, 4, 5), True, None, None, 1.0), "erosion"),
+    (((2, 3, 4, 5), 5, None, 2, None, None, 1.0), "erosion=2 without a mask"),
+    (((2, 3, 4, 5), 5, (2, 3, 4, 6), 0, None, None, 1.0), "mask"),
+    (((2, 1, 3, 4, 5), 5, (2, 3, 4, 5), 0, None, None, 1.0), "mask"),
+    (((2, 3, 4, 5), 5, None, 0, (2, 3, 4, 6), None, 1.0), "labels"),
+    (((2, 3, 4, 5), 5, None, 0, None, float("nan"), 1.0), "threshold"),
+    (((2, 3, 4, 5), 5, None, 0, None, float("inf"), 1.0), "threshold"),
+    (((2, 3, 4, 5), 5, None, 0, None, 1e39, 1.0), "threshold"),
+    (((2, 3, 4, 5), 5, None, 0, None, "high", 1.0), "threshold"),
+    (((2, 3, 4, 5), 5, None, 0, None, None, 0.0), "hist_max"),
+    (((2, 3, 4, 5), 5, None, 0, None, None, -1.0), "hist_max"),
+    (((2, 3, 4, 5), 5, None, 0, None, None, float("inf")), "hist_max"),
+    (((2, 3, 4, 5), 5, None, 0, None, None, float("nan")), "hist_max"),
+    (((2, 3, 4, 5), 5, None, 0, None, None, 1e-40), "hist_max"),
+    (((2, 3, 4, 5), 5, None, 0, None, None, "wide"), "hist_max"),
+])
+def test_check_arguments_refuses_by_name(args, match):
+    with pytest.raises(ValueError, match=match):
+        M.check_arguments(*args)
+
+
+def test_median_filter_map_refuses_before_any_launch_and_has_no_cpu_path(monkeypatch):
+    from synthanatomy_amd import _ffi
+
+    def touched():
+        raise AssertionError("the device was asked for")
+    monkeypatch.setattr(_ffi, "require_gpu", touched)
+    a = torch.zeros(2, 1, 3, 4, 5)
+    for kw, match in ((dict(size=4), "size"), (dict(erosion=1), "without a mask"), (dict(mask=torch.ones(2, 1, 3, 4, 5), erosion=5), "erosion"),
+                      (dict(mask=torch.ones(2, 1, 3, 4, 4)), "mask"), (dict(labels=torch.zeros(2, 1, 3, 4, 4)), "labels"),
+                      (dict(threshold=float("nan")), "threshold"), (dict(hist_max=0), "hist_max")):
+        with pytest.raises(ValueError, match=match):
+            M.median_filter_map(a, **kw)
+    with pytest.raises(ValueError, match="volumes"):
+        M.median_filter_map(torch.zeros(3, 4, 5))
+    with pytest.raises(AssertionError, match="the device was asked for"):      # valid arguments go on to the device: there is nothing else to run
+        M.median_filter_map(a)
+
+
+# ---- the flags ----
+
+class _DeviceTouched(Exception):
+    pass
+
+
+@pytest.fixture
+def no_device(monkeypatch):
+    from synthanatomy_amd.runtime import ddp
+
+    def touched():
+        raise _DeviceTouched()
+    monkeypatch.setattr(ddp, "init_distributed", touched)
+    monkeypatch.setattr(torch.cuda, "is_available", touched)
+
+
+def _argv(tmp_path, *extra, mode="anomaly"):
+    return ["run", "--training_subjects=synthetic:2", "--validation_subjects=synthetic:2", f"--project_directory={tmp_path}/", "--experiment_name=e",
+            f"--mode={mode}", *extra]
+
+
+def test_the_flags_their_defaults_and_a_full_command_line(tmp_path, no_device):
+    from synthanatomy_amd.utils.general import parse_flags
+    D = RV.DEFAULTS
+    assert (D["anomaly_median"], D["anomaly_mask"], D["anomaly_mask_threshold"], D["anomaly_mask_erosion"]) == (None, None, 0.0, 0)
+    cfg = parse_flags(_argv(tmp_path, "--anomaly_median=3", "--anomaly_mask=scan", "--anomaly_mask_threshold=0.125", "--anomaly_mask_erosion=2"), D)
+    assert (cfg["anomaly_median"], cfg["anomaly_mask"], cfg["anomaly_mask_threshold"], cfg["anomaly_mask_erosion"]) == (3, "scan", 0.125, 2)
+    RV._check_anomaly_flags(cfg)
+    for extra in (("--anomaly_median=5",), ("--anomaly_mask=scan",), ("--anomaly_mask=/masks", "--anomaly_mask_erosion=4"), ("--anomaly_median=1",),
+                  ("--anomaly_mask=scan", "--anomaly_mask_threshold=-1", "--anomaly_median=3", "--anomaly_threshold=0.1", "--anomaly_min_component=2")):
+        with pytest.raises(_DeviceTouched):
+            RV.run(_argv(tmp_path, *extra))
+    for flag in ("--anomaly_median", "--anomaly_mask=scan", "--anomaly_mask_threshold", "--anomaly_mask_erosion", "_anomaly_map_filtered", "filtered_sum"):
+        assert flag in RV.__doc__
+
+
+@pytest.mark.parametrize("extra, match", [
+    (("--anomaly_median=2",), "--anomaly_median=2"),
+    (("--anomaly_median=7",), "--anomaly_median=7"),
+    (("--anomaly_median=3.0",), "--anomaly_median=3.0"),
+    (("--anomaly_median=True",), "--anomaly_median=True"),
+    (("--anomaly_median=five",), "--anomaly_median=five"),
+    (("--anomaly_mask=3",), "--anomaly_mask=3"),
+    (("--anomaly_mask=True",), "--anomaly_mask=True"),
+    (("--anomaly_mask_threshold=0.5",), r"--anomaly_mask_threshold=0.5.*--anomaly_mask=scan"),
+    (("--anomaly_mask=/masks", "--anomaly_mask_threshold=0.5"), r"--anomaly_mask_threshold=0.5.*--anomaly_mask=scan"),
+    (("--anomaly_mask=scan", "--anomaly_mask_threshold=nan"), "--anomaly_mask_threshold=nan"),
+    (("--anomaly_mask=scan", "--anomaly_mask_threshold=high"), "--anomaly_mask_threshold=high"),
+    (("--anomaly_mask=scan", "--anomaly_mask_threshold=None"), "--anomaly_mask_threshold=None"),
+    (("--anomaly_mask_erosion=1",), r"--anomaly_mask_erosion=1.*--anomaly_mask"),
+    (("--anomaly_median=3", "--anomaly_mask_erosion=2"), r"--anomaly_mask_erosion=2.*--anomaly_mask"),
+    (("--anomaly_mask=scan", "--anomaly_mask_erosion=5"), "--anomaly_mask_erosion=5"),
+    (("--anomaly_mask=scan", "--anomaly_mask_erosion=-1"), "--anomaly_mask_erosion=-1"),
+    (("--anomaly_mask=scan", "--anomaly_mask_erosion=1.5"), "--anomaly_mask_erosion=1.5"),
+    (("--anomaly_mask=scan", "--anomaly_mask_erosion=None"), "--anomaly_mask_erosion=None"),
+])
+def test_a_bad_flag_is_refused_by_name_before_the_device(tmp_path, no_device, extra, match):
+    with pytest.raises(ValueError, match=match):
+        RV.run(_argv(tmp_path, *extra))
+    assert not os.path.exists(tmp_path / "e")
+
+
+@pytest.mark.parametrize("mode", ["training", "extracting", "decoding"])
+@pytest.mark.parametrize("flag", ["--anomaly_median=3", "--anomaly_mask=scan", "--anomaly_mask_threshold=0.5", "--anomaly_mask_erosion=1"])
+def test_the_flags_belong_to_the_anomaly_mode(tmp_path, no_device, mode, flag):
+    with pytest.raises(ValueError, match=flag + r".*--mode=anomaly, not --mode=" + mode):
+        RV.run(_argv(tmp_path, flag, mode=mode))
+    assert not os.path.exists(tmp_path / "e")
+
+
+# ---- the ABI ----
+
+def _header():
+    with open(os.path.join(ROOT, "include", "synthanatomy_hip.h")) as f:
+        return f.read()
+
+
+def test_the_header_and_the_bindings_name_the_two_symbols_and_the_abi_version_stays():
+    from synthanatomy_amd import _ffi
+    text = _header()
+    assert re.search(r"\bint sa_anomaly_median\(const float \*a, const unsigned char \*mask, const unsigned char \*label, float \*out, "
+                     r"const sa_median_params \*params,\s+void \*results, void \*ws, void \*stream\);", text)
+    assert re.search(r"\bint64_t sa_anomaly_median_workspace_bytes\(const sa_median_params \*params\);", text)
+    assert {"sa_anomaly_median", "sa_anomaly_median_workspace_bytes"} <= set(_ffi.declared_symbols())
+    assert _ffi.ABI_VERSION == 5 and re.search(r"#define SA_ABI_VERSION 5\b", text)
+    assert "no reference counterpart" in text[text.index("Masked 3-D median filter"):text.index("sa_median_params {")]
+    tile = tuple(int(re.search(rf"SA_MEDIAN_TILE_{ax} = (\d+)", text).group(1)) for ax in "DHW")
+    assert M.TILE == tile == _ffi.MEDIAN_TILE
+    assert int(re.search(r"SA_MEDIAN_MAX_EROSION = (\d+)", text).group(1)) == M.MAX_EROSION == _ffi.MEDIAN_MAX_EROSION
+    assert re.search(r"\} sa_median_params; /\* 44 bytes \*/", text)
+
+
+def test_the_params_struct_the_library_and_its_host_side_refusals():
+    from synthanatomy_amd import _ffi
+    from synthanatomy_amd.build import build
+    P = _ffi.MedianParams
+    assert ctypes.sizeof(P) == 44
+    assert [f[0] for f in P._fields_] == ["B", "D", "H", "W", "size", "erosion", "has_mask", "has_labels", "has_threshold", "inv_bin", "threshold"]
+    assert P.size.offset == 16 and P.inv_bin.offset == 36 and P.threshold.offset == 40
+    lib = ctypes.CDLL(build(verbose=False))
+    q = lib.sa_anomaly_median_workspace_bytes
+    q.restype, q.argtypes = ctypes.c_int64, [ctypes.POINTER(P)]
+    run = lib.sa_anomaly_median
+    run.restype = ctypes.c_int
+    run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(P), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+    def good(**kw):
+        base = dict(B=2, D=19, H=21, W=67, size=5, erosion=0, has_mask=0, has_labels=0, has_threshold=0, inv_bin=256.0, threshold=0.0)
+        base.update(kw)
+        return P(**base)
+    assert q(None) == _ffi.SA_EINVAL
+    # positive, and monotone in every side, in the batch and in the erosion buffers
+    sizes = [q(ctypes.byref(good(**kw))) for kw in (dict(D=1, H=1, W=1, B=1), dict(B=1), dict(), dict(D=40), dict(D=40, H=40), dict(D=40, H=40, W=100),
+                                                   dict(D=40, H=40, W=100, B=3))]
+    assert sizes[0] > 0 and all(a <= b for a, b in zip(sizes, sizes[1:])) and sizes[0] < sizes[-1]
+    eroded = [q(ctypes.byref(good(has_mask=1, erosion=e))) for e in range(5)]
+    assert eroded[0] == sizes[2] and eroded[0] < eroded[1] < eroded[2] == eroded[3] == eroded[4]
+    assert eroded[2] - eroded[0] >= 2 * 2 * 19 * 21 * 67
+    refused = [("size", 0), ("size", 2), ("size", 7), ("erosion", -1), ("erosion", 5), ("B", 0), ("D", 0), ("H", -1), ("W", 0), ("inv_bin", 0.0),
+               ("inv_bin", -1.0), ("inv_bin", float("inf")), ("inv_bin", float("nan"))]
+    for field, bad in refused:
+        Q = good(has_mask=1, **{field: bad})
+        assert q(ctypes.byref(Q)) == _ffi.SA_EINVAL, (field, bad)
+        assert run(256, 512, None, 1024, ctypes.byref(Q), 2048, 4096, None) == _ffi.SA_EINVAL, (field, bad)
+    assert q(ctypes.byref(good(erosion=1))) == _ffi.SA_EINVAL                                          # erosion without a mask
+    assert q(ctypes.byref(good(has_threshold=1, threshold=float("nan")))) == _ffi.SA_EINVAL
+    assert q(ctypes.byref(good(has_threshold=1, threshold=float("inf")))) == _ffi.SA_EINVAL
+    assert q(ctypes.byref(good(has_threshold=0, threshold=float("nan")))) > 0                          # not read without the flag
+    assert q(ctypes.byref(good(B=65536))) == _ffi.SA_EUNSUPPORTED
+    assert q(ctypes.byref(good(D=1 << 11, H=1 << 10, W=1 << 10))) == _ffi.SA_EUNSUPPORTED
+    assert q(ctypes.byref(good(B=1, D=2 ** 31 - 1, H=1, W=1))) == _ffi.SA_EUNSUPPORTED
+    assert q(ctypes.byref(good(B=1, D=2 ** 31 - 2, H=1, W=1))) > 0
+    # the entry point refuses null operands, pointers that disagree with their flags and out == a before it touches a device
+    ok = good()
+    assert run(None, None, None, 1024, ctypes.byref(ok), 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, None, ctypes.byref(ok), 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, None, 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, ctypes.byref(ok), None, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, ctypes.byref(ok), 2048, None, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 256, ctypes.byref(ok), 2048, 4096, None) == _ffi.SA_EINVAL             # out == a
+    assert run(256, 512, None, 1024, ctypes.byref(ok), 2048, 4096, None) == _ffi.SA_EINVAL             # a mask the params do not announce
+    assert run(256, None, 512, 1024, ctypes.byref(ok), 2048, 4096, None) == _ffi.SA_EINVAL             # labels the params do not announce
+    assert run(256, None, None, 1024, ctypes.byref(good(has_mask=1)), 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, ctypes.byref(good(has_labels=1)), 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, ctypes.byref(good(erosion=1)), 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, ctypes.byref(good(has_threshold=1, threshold=float("inf"))), 2048, 4096, None) == _ffi.SA_EINVAL
+    assert run(256, None, None, 1024, ctypes.byref(good(B=65536)), 2048, 4096, None) == _ffi.SA_EUNSUPPORTED
