@@ -101,6 +101,8 @@ int sa_kernel_log_read(char *buf, int cap, int stop);
 #define SA_DBG_NO_CLASS_LAUNCH    (1u << 22)  /* sa_conv_fprop_classes answers SA_EUNSUPPORTED: the parity classes of a transposed convolution as separate launches (A/B, equality test) */
 #define SA_DBG_NO_STRIP_TILES     (1u << 23)  /* two-plane 3x3x3 halo tiles: the last 1..8 columns of a plane on ordinary 8 x 16 tiles instead of 16 x 8 strip tiles (A/B, equality test) */
 #define SA_DBG_GENERIC_EPILOGUE   (1u << 24)  /* register epilogue of the eight-wave halo / cell kernels: the generic code instead of the launch's compile-time recipe (A/B, equality test) */
+#define SA_DBG_WGRAD9_LOCKSTEP    (1u << 25)  /* nine-tap weight gradient: the step body with one full DMA wait + barrier per step and per-step address arithmetic, as before the schedule rework (A/B, equality test) */
+#define SA_DBG_WGRAD9_FORCE       (1u << 26)  /* test aid: every 3x3x3 stride-1 C = 128 bf16 weight gradient on the nine-tap kernel, whatever its step count and tile efficiency, in blocks of at most three steps (default: from 512 steps at >= 80 %, at least 16 steps per block): small shapes reach the kernel, one-step blocks included */
 #define SA_DBG_FAVOR_SEQ_ALWAYS (1u << 18)  /* FAVOR+ chunk states in the sequential form for every batch (default: from 40 (batch, head) pairs; tests) */
 #define SA_DBG_DETERMINISTIC     (1u << 16)  /* fixed-order reductions where the library itself chooses (BatchNorm sums); see the deterministic-mode section */
 #define SA_DBG_SCAN_EXACT_SHIFT  10          /* 3 bits: chunk states | scan A outputs | scan B outputs on the exact-fp32 MFMA kernels */
@@ -174,6 +176,10 @@ int sa_conv1x1_backward(const sa_conv_geom *g, int dtype, const void *in, const 
 /* bytes of scratch sa_conv_wgrad wants for this geometry (partial tiles of the voxel splits; a second kernel reduces them
  * without atomics).  With workspace == NULL the kernel falls back to fp32 atomics straight into dw. */
 int64_t sa_conv_wgrad_workspace_bytes(const sa_conv_geom *g, int dtype);
+/* test aid (host only, no device): the step walk of the nine-tap 3x3x3 weight-gradient kernel.  A step is 8 x 16 voxels of one plane,
+ * step = ((n * Dm + d) * HQ + hq) * WP + wp; a block decomposes its first step and carries the counters.  Writes (wp, hq, d, n) of the steps
+ * step0 .. step0 + count - 1 as the kernel carries them from step0 into out[count][4]; SA_EINVAL for a zero extent or a NULL out. */
+int sa_wgrad9_step_walk(uint32_t WP, uint32_t HQ, uint32_t Dm, uint32_t step0, uint32_t count, uint32_t *out);
 
 /* db[c] += sum_m g[m][c]   (bias gradient), g is [M][cstride] of dtype */
 int sa_colsum(const void *g, int dtype, int64_t M, int C, int cstride, float *db, void *stream);

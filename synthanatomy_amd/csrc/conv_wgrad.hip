@@ -13,6 +13,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "sa_common.h"
 
 namespace sa {
@@ -36,6 +38,7 @@ struct WgradArgs {
     void* dg_out;         // [M][128] bf16
     // halo kernel (3x3x3 stride 1, bf16, Cin = 128): the voxel range is walked in steps of 4 (H) x 16 (W) voxels
     uint32_t HQ, WP, nsteps, steps_per_split, halo;
+    uint32_t wg9_lockstep;   // nine-tap kernel: the lock-step step body (SA_DBG_WGRAD9_LOCKSTEP)
     FastDiv dWP, dHQ;
 };
 
@@ -714,6 +717,63 @@ __global__ __launch_bounds__(768) void conv_wgrad_halo_kernel(const WgradArgs a)
 // distinct 32-byte bank groups (rows of equal parity share a 256-byte bank line).
 __device__ __forceinline__ uint32_t roff128(uint32_t m, uint32_t c) { return m * 128u + ((((c >> 4) ^ ((m >> 1) & 3u)) << 5) | ((c & 15u) << 1)); }
 
+// Step walk of the nine-tap kernel: step = ((n * Dm + d) * HQ + hq) * WP + wp.  A block walks consecutive steps, so it decomposes its first step once
+// (wgrad9_walk_at) and carries the four counters from step to step (wgrad9_walk_next): block-uniform, scalar registers, no division in the step.
+struct Wgrad9Walk {
+    uint32_t wp, hq, d, n;
+};
+__host__ __device__ inline Wgrad9Walk wgrad9_walk_at(uint32_t step, uint32_t WP, uint32_t HQ, uint32_t Dm) {
+    Wgrad9Walk w;
+    const uint32_t q1 = step / WP, q2 = q1 / HQ;
+    w.wp = step - q1 * WP;
+    w.hq = q1 - q2 * HQ;
+    w.n = q2 / Dm;
+    w.d = q2 - w.n * Dm;
+    return w;
+}
+__host__ __device__ inline void wgrad9_walk_next(Wgrad9Walk& w, uint32_t WP, uint32_t HQ, uint32_t Dm) {
+    if (++w.wp != WP) return;
+    w.wp = 0;
+    if (++w.hq != HQ) return;
+    w.hq = 0;
+    if (++w.d != Dm) return;
+    w.d = 0;
+    ++w.n;
+}
+
+__device__ __forceinline__ v4s_t lds_tr16_at(uint32_t addr) {   // LDS byte address (a constant addend folds into the instruction's offset field)
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)(size_t)addr);
+}
+
+#ifdef SA_TIMING
+// dev instrumentation (-DSA_TIMING): s_memtime sums of waves 0 and 4 (the two waves of SIMD 0) of every block of the nine-tap kernel, kept in registers and
+// written by ONE vector store per block (16 lanes x 8 bytes): row = blockIdx.x, [0..7] wave 0, [8..15] wave 4; slots: 0 issue (address arithmetic + DMA issue),
+// 1 colsum, 2 reads (first transposing read of a K step .. first operand pair back), 3 mfma (rest of the K step), 4 dma_wait, 5 barrier, 6 prologue, 7 epilogue
+#define SA_WG9_TROWS 4096
+__device__ unsigned long long g_wg9_timing[SA_WG9_TROWS * 16];
+#define WG9_TNOW(v)                                                                                  \
+    do {                                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                           \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");                     \
+        __builtin_amdgcn_sched_barrier(0);                                                           \
+    } while (0)
+#define WG9_T(slot)                          \
+    do {                                     \
+        unsigned long long t_now_;           \
+        WG9_TNOW(t_now_);                    \
+        wg9_ts[slot] += t_now_ - wg9_tprev;  \
+        wg9_tprev = t_now_;                  \
+    } while (0)
+#else
+#define WG9_T(slot)
+#endif
+
+// Schedule switch of the default (not SA_DBG_WGRAD9_LOCKSTEP) step body, for A/B builds: SA_WG9_STAGGER = 0 issues the next step's DMA at the top of the step in
+// all eight waves, as the lock-step body does.
+#ifndef SA_WG9_STAGGER
+#define SA_WG9_STAGGER 1
+#endif
+
 // NW = 16: the same step worked by sixteen waves (36 x 2 accumulator fragments each, <= 128 VGPRs -> four waves per SIMD from ONE block: the
 // 110 KiB of LDS allow no second block, and two waves per SIMD leave the MFMA pipe idle through every DMA wait / barrier).
 template <int NW>
@@ -802,9 +862,10 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_halo9_kernel(const WgradAr
         }
     };
 
-    issue(step0, 0);
-    dma_wait();
-    __syncthreads();
+#ifdef SA_TIMING
+    unsigned long long wg9_ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wg9_tprev;
+    WG9_TNOW(wg9_tprev);
+#endif
     const uint32_t frow = lane & 15u, fq = lane >> 4;
     const uint32_t trow = fq * 4u + (frow >> 2), tcol = (frow & 3u) * 4u;
     const bool do_db = a.db != nullptr && tdc == 0u;   // one of the six blocks of a split also sums the gradient rows
@@ -822,37 +883,171 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_halo9_kernel(const WgradAr
     uint32_t ga[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) ga[j] = roff(trow, wn * (16 * NJ) + j * 16 + tcol);   // (+ 4096 for the high half: 16 rows keep m & 7)
-    for (uint32_t st = step0; st < step1; ++st) {
-        const uint32_t buf = (st - step0) & 1u;
-        if (st + 1 < step1) issue(st + 1, buf ^ 1u);
-        const unsigned char* px = smem + buf * STAGE;
-        const unsigned char* pg = px + XT;
-        if (do_db) tile_colsum<128, NW>(pg, tid, bs0, bs1);
+    // The default step body needs the stage base on a 128-byte boundary (it flips byte bit 6 of base + offset); a block that is not gets the lock-step body.
+    // NW = 16 (an A/B instance) keeps the lock-step body: the unrolled one does not fit its 128 registers.
+    const bool lockstep = NW != 8 || a.wg9_lockstep != 0u || (smem_addr & 127u) != 0u;
+    if (lockstep) {
+        // SA_DBG_WGRAD9_LOCKSTEP: the step as it was before the schedule rework -- per-step decomposition of the step index, per-piece bounds tests, a rolled
+        // K-step loop with run-time operand addresses, one full DMA wait and one barrier per step.  Same pieces, same MFMAs in the same order: bit-identical.
+        issue(step0, 0);
+        dma_wait();
+        __syncthreads();
+        WG9_T(6);
+        for (uint32_t st = step0; st < step1; ++st) {
+            const uint32_t buf = (st - step0) & 1u;
+            if (st + 1 < step1) issue(st + 1, buf ^ 1u);
+            WG9_T(0);
+            const unsigned char* px = smem + buf * STAGE;
+            const unsigned char* pg = px + XT;
+            if (do_db) tile_colsum<128, NW>(pg, tid, bs0, bs1);
+            WG9_T(1);
 #pragma unroll 1
-        for (uint32_t ks = 0; ks < 4; ++ks) {   // 32 voxels = patch rows 2 ks, 2 ks + 1  (rolled: unrolling spills the 144 accumulators)
+            for (uint32_t ks = 0; ks < 4; ++ks) {   // 32 voxels = patch rows 2 ks, 2 ks + 1  (rolled: unrolling spills the 144 accumulators)
+                short8_t gf[NJ];
+                const unsigned char* pgk = pg + ks * 8192u;
+                const unsigned char* pxk = px + ks * 4608u;
+                const uint32_t kx = (ks & 1u) * 64u;
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const v4s_t lo = lds_tr16(pgk + ga[j]);
+                    const v4s_t hi = lds_tr16(pgk + ga[j] + 4096);
+                    gf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                }
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const v4s_t lo = lds_tr16(pxk + (xa[t][0] ^ kx));
+                    const v4s_t hi = lds_tr16(pxk + (xa[t][1] ^ kx));
+                    const short8_t xf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    if (t == 0) WG9_T(2);
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf, gf[j], acc[t][j], 0, 0, 0);
+                }
+                WG9_T(3);
+            }
+            dma_wait();       // the next step's tiles have landed (the compiler does not know about them: dma16_hidden)
+            WG9_T(4);
+            __syncthreads();  // ... in every wave, and this buffer is free
+            WG9_T(5);
+        }
+    } else {
+        // Default step body.  Against the lock-step one:
+        //  * the step index is walked with carried counters (Wgrad9Walk) and the in-volume test of a piece row is one AND: a row can leave the volume only in
+        //    the first / last row block (hq) and column block (wp) of a plane, so each lane keeps, per piece, a 6-bit field "invalid when ..." (bit 0 hq == 0,
+        //    1 hq == HQ - 1, 2 wp == 0, 3 wp == WP - 1, 4 always: rows 180..183, 5 input depth outside: activation pieces) and the step supplies the
+        //    block-uniform mask of the conditions that hold;
+        //  * the four K steps are unrolled and every operand address is `stage address register + immediate`: K step ks adds ks * 4608 / ks * 8192 bytes and
+        //    flips byte bit 6 of the halo addresses on odd ks (one XOR; the stage base is a multiple of 128, so the flip commutes with adding it); the
+        //    registers move to the other stage once per step;
+        //  * (SA_WG9_STAGGER) the two waves of a SIMD issue their share of the next step's DMA at different times: waves 0..3 at the top of the step,
+        //    waves 4..7 after K step 0.  The phase stamps show the issue of a step's 55 KiB held back by the vector-memory path for 800 - 1 400 cycles per step
+        //    with both waves of every SIMD in it at once, the MFMA pipe empty; staggered, one wave of each SIMD multiplies while the other issues.
+        // Pieces, stage layout, MFMA operands and the (step, ks, tap, j) order per accumulator are the lock-step body's: dw and db are bit-identical.
+        __builtin_assume(wave < (uint32_t)NW);
+        constexpr int NPM = (PPW + 4) / 5;
+        uint32_t pm[NPM];
+#pragma unroll
+        for (int i = 0; i < NPM; ++i) pm[i] = 0u;
+        const int32_t hl = (int32_t)(a.HQ - 1u) * 8, wl = (int32_t)(a.WP - 1u) * 16;
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+            const uint32_t q = wave + (uint32_t)NW * i;
+            uint32_t f;
+            if (q < (uint32_t)XP)
+                f = (p_h[i] < 0 ? 1u : 0u) | (hl + p_h[i] >= g.Hi ? 2u : 0u) | (p_w[i] < 0 ? 4u : 0u) | (wl + p_w[i] >= g.Wi ? 8u : 0u) | (p_h[i] < -1 ? 16u : 0u) | 32u;
+            else
+                f = (hl + p_h[i] >= g.Ho ? 2u : 0u) | (wl + p_w[i] >= g.Wo ? 8u : 0u);
+            pm[i / 5] |= f << (6 * (i % 5));
+        }
+        auto issue2 = [&](const Wgrad9Walk& w, uint32_t buf) __attribute__((always_inline)) {
+            const uint32_t ps = smem_addr + buf * STAGE;
+            const int32_t h0 = (int32_t)w.hq * 8, w0 = (int32_t)w.wp * 16;
+            const int32_t id = (int32_t)w.d + g.in_off[0] + (int32_t)td;
+            const bool dok = (uint32_t)id < (uint32_t)g.Di;
+            const uint32_t xbase = (uint32_t)((((int32_t)w.n * g.Di + id) * g.Hi + h0) * g.Wi + w0) * (uint32_t)(g.Cin * 2);
+            const uint32_t gbase = (uint32_t)((((int32_t)w.n * g.Do + (int32_t)w.d) * g.Ho + h0) * g.Wo + w0) * (uint32_t)(g.Cout * 2);
+            const uint32_t em = (w.hq == 0u ? 1u : 0u) | (w.hq + 1u == a.HQ ? 2u : 0u) | (w.wp == 0u ? 4u : 0u) | (w.wp + 1u == a.WP ? 8u : 0u) | 16u | (dok ? 0u : 32u);
+#pragma unroll
+            for (int i = 0; i < PPW; ++i) {
+                const uint32_t q = wave + (uint32_t)NW * i;
+                if (q >= (uint32_t)NP) break;
+                const bool ok = (pm[i / 5] & (em << (6 * (i % 5)))) == 0u;
+                if (q < (uint32_t)XP) dma16_hidden(rX, ps + q * 1024, ok ? xbase + p_off[i] : 0xfffffff0u);
+                else dma16_hidden(rG, ps + XT + (q - (uint32_t)XP) * 1024, ok ? gbase + p_off[i] : 0xfffffff0u);
+            }
+        };
+        Wgrad9Walk walk;
+        {
+            const uint32_t q1 = fdiv(step0, a.dWP), q2 = fdiv(q1, a.dHQ);
+            walk.wp = step0 - q1 * a.WP;
+            walk.hq = q1 - q2 * a.HQ;
+            walk.n = fdiv(q2, a.dD);
+            walk.d = q2 - walk.n * (uint32_t)g.Dm;
+        }
+        issue2(walk, 0);
+        // operand addresses in stage 0
+        uint32_t xr[9][2], gr[NJ];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            xr[t][0] = smem_addr + xa[t][0];
+            xr[t][1] = smem_addr + xa[t][1];
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) gr[j] = smem_addr + (uint32_t)XT + ga[j];
+        auto kstep = [&](auto ksc) __attribute__((always_inline)) {   // 32 voxels = patch rows 2 ks, 2 ks + 1
+            constexpr uint32_t KS = decltype(ksc)::value;
             short8_t gf[NJ];
-            const unsigned char* pgk = pg + ks * 8192u;
-            const unsigned char* pxk = px + ks * 4608u;
-            const uint32_t kx = (ks & 1u) * 64u;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const v4s_t lo = lds_tr16(pgk + ga[j]);
-                const v4s_t hi = lds_tr16(pgk + ga[j] + 4096);
+                const v4s_t lo = lds_tr16_at(gr[j] + KS * 8192u);
+                const v4s_t hi = lds_tr16_at(gr[j] + KS * 8192u + 4096u);
                 gf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
-                const v4s_t lo = lds_tr16(pxk + (xa[t][0] ^ kx));
-                const v4s_t hi = lds_tr16(pxk + (xa[t][1] ^ kx));
+                const v4s_t lo = lds_tr16_at((xr[t][0] ^ ((KS & 1u) * 64u)) + KS * 4608u);
+                const v4s_t hi = lds_tr16_at((xr[t][1] ^ ((KS & 1u) * 64u)) + KS * 4608u);
                 const short8_t xf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                if (t == 0) WG9_T(2);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf, gf[j], acc[t][j], 0, 0, 0);
             }
+            WG9_T(3);
+            __builtin_amdgcn_sched_barrier(0);   // keep the K steps apart: reads hoisted across them spill the 144 accumulators
+        };
+        dma_wait();
+        __syncthreads();
+        WG9_T(6);
+        const bool late = SA_WG9_STAGGER && wave >= (uint32_t)NW / 2u;   // the second wave of each SIMD issues after K step 0
+        for (uint32_t st = step0; st < step1; ++st) {
+            const uint32_t buf = (st - step0) & 1u;
+            const bool more = st + 1 < step1;
+            if (more) wgrad9_walk_next(walk, a.WP, a.HQ, (uint32_t)g.Dm);
+            if (more && !late) issue2(walk, buf ^ 1u);
+            WG9_T(0);
+            if (do_db) tile_colsum<128, NW>(smem + buf * STAGE + XT, tid, bs0, bs1);
+            WG9_T(1);
+            kstep(std::integral_constant<uint32_t, 0>{});
+            if (more && late) issue2(walk, buf ^ 1u);
+            WG9_T(0);
+            kstep(std::integral_constant<uint32_t, 1>{});
+            kstep(std::integral_constant<uint32_t, 2>{});
+            kstep(std::integral_constant<uint32_t, 3>{});
+            const uint32_t flip = buf ? 0u - (uint32_t)STAGE : (uint32_t)STAGE;   // operand addresses -> the other stage
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                xr[t][0] += flip;
+                xr[t][1] += flip;
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) gr[j] += flip;
+            dma_wait();       // the next step's tiles have landed (the compiler does not know about them: dma16_hidden)
+            WG9_T(4);
+            __syncthreads();  // ... in every wave, and this buffer is free
+            WG9_T(5);
         }
-        dma_wait();       // the next step's tiles have landed (the compiler does not know about them: dma16_hidden)
-        __syncthreads();  // ... in every wave, and this buffer is free
     }
     if (do_db) colsum_finish<NW>((float*)smem, tid, bs0, bs1, a.db, ct * 128u, (uint32_t)g.cout_valid);
+    WG9_T(1);
     // partial tiles of the nine taps of this kd -> workspace [split][tile = tap + 27*ct][co 128][ci 128]
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
@@ -860,8 +1055,39 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_halo9_kernel(const WgradAr
 #pragma unroll
         for (int j = 0; j < NJ; ++j) *(float4_t*)(wt + (wn * (16 * NJ) + j * 16 + frow) * 128 + cih * 64 + fi * 16 + fq * 4) = acc[t][j];
     }
+#ifdef SA_TIMING
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    WG9_T(7);
+    {
+        // waves 0 and 4 park their sums in LDS (free by now); lanes 0..15 of wave 0 write the block's row with one store instruction
+        unsigned long long* tl = (unsigned long long*)smem;
+        __syncthreads();
+        if ((wave == 0u || wave == (uint32_t)NW / 2u) && lane < 8u) {
+            unsigned long long v = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (lane == (uint32_t)k) v = wg9_ts[k];
+            tl[(wave ? 8u : 0u) + lane] = v;
+        }
+        __syncthreads();
+        if (tid < 16u && blockIdx.x < (uint32_t)SA_WG9_TROWS) g_wg9_timing[blockIdx.x * 16u + tid] += tl[tid];
+    }
+#endif
 #endif
 }
+
+#ifdef SA_TIMING
+}  // namespace sa
+extern "C" int sa_debug_timing_wgrad9(unsigned long long* out, int reset) {   // out: SA_WG9_TROWS x 16 sums (rows of blocks that never ran stay 0)
+    if (out) hipMemcpyFromSymbol(out, HIP_SYMBOL(sa::g_wg9_timing), sizeof(unsigned long long) * SA_WG9_TROWS * 16);
+    if (reset) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(sa::g_wg9_timing)) == hipSuccess) hipMemset(p, 0, sizeof(unsigned long long) * SA_WG9_TROWS * 16);
+    }
+    return 0;
+}
+namespace sa {
+#endif
 
 // dw[co][ci][tap] += sum_split ws[split][tile][co][kidx]   (no atomics).  One thread owns 4 consecutive kidx of one (tile, co) and
 // streams the splits with 8 independent 16-byte loads in flight.
@@ -1045,6 +1271,7 @@ static int plan_wgrad(const sa_conv_geom* g, int dtype, WgradArgs& a, uint32_t& 
     splits = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
     // halo kernel: 3x3x3 / stride 1 / same, bf16, 128 input channels, both operands addressable with 32-bit offsets
     a.halo = 0;
+    a.wg9_lockstep = dbg(SA_DBG_WGRAD9_LOCKSTEP) ? 1u : 0u;
     {
         bool ok = dtype == SA_BF16 && g->Cin == 128 && g->cin_valid == 128 && g->Cout % 128 == 0 && !dbg(SA_DBG_NO_HALO) && !dbg(SA_DBG_NO_DMA);
         for (int d = 0; d < 3 && ok; ++d)
@@ -1059,7 +1286,9 @@ static int plan_wgrad(const sa_conv_geom* g, int dtype, WgradArgs& a, uint32_t& 
             const uint32_t hq = (uint32_t)(g->Ho + phs - 1) / phs, wp = (uint32_t)(g->Wo + 15) / 16;
             const double eff = (double)g->Ho * g->Wo / ((double)hq * phs * wp * 16);
             const uint64_t nsteps = (uint64_t)g->N * g->Dm * hq * wp;
-            if (eff >= 0.8 && nsteps >= 512) {
+            // SA_DBG_WGRAD9_FORCE (test aid): the nine-tap kernel for any step count and efficiency, for launches the default rule leaves to other kernels in blocks of at most three steps (up to the usual split count)
+            const bool force9 = nine && dbg(SA_DBG_WGRAD9_FORCE) && nsteps < (1ull << 31);
+            if ((eff >= 0.8 && nsteps >= 512) || force9) {
                 a.halo = nine ? 9u : 4u;
                 a.HQ = hq;
                 a.WP = wp;
@@ -1069,6 +1298,10 @@ static int plan_wgrad(const sa_conv_geom* g, int dtype, WgradArgs& a, uint32_t& 
                 const int want = g_tunables.wgrad_halo_splits ? g_tunables.wgrad_halo_splits : (nine ? 128 : 256);
                 uint32_t sp = (uint32_t)want;
                 if (sp > a.nsteps / 16) sp = a.nsteps / 16;   // at least 16 steps per block
+                if (force9 && !(eff >= 0.8 && nsteps >= 512)) {   // a launch the default rule would not take: short blocks, the one-step block included
+                    sp = a.nsteps >= 6 ? (a.nsteps + 2) / 3 : 2;
+                    if (sp > (uint32_t)want) sp = (uint32_t)want;
+                }
                 if (sp < 1) sp = 1;
                 a.steps_per_split = (a.nsteps + sp - 1) / sp;
                 splits = (a.nsteps + a.steps_per_split - 1) / a.steps_per_split;
@@ -1087,6 +1320,16 @@ extern "C" int64_t sa_conv_wgrad_workspace_bytes(const sa_conv_geom* g, int dtyp
     const int rc = plan_wgrad(g, dtype, a, splits);
     if (rc) return rc;
     return (int64_t)splits * a.ntiles * 128 * 128 * 4;
+}
+
+extern "C" int sa_wgrad9_step_walk(uint32_t WP, uint32_t HQ, uint32_t Dm, uint32_t step0, uint32_t count, uint32_t* out) {
+    if (!WP || !HQ || !Dm || !out) return SA_EINVAL;
+    sa::Wgrad9Walk w = sa::wgrad9_walk_at(step0, WP, HQ, Dm);
+    for (uint32_t i = 0; i < count; ++i) {
+        out[4 * i + 0] = w.wp, out[4 * i + 1] = w.hq, out[4 * i + 2] = w.d, out[4 * i + 3] = w.n;
+        sa::wgrad9_walk_next(w, WP, HQ, Dm);
+    }
+    return 0;
 }
 
 extern "C" int sa_colsum(const void* gp, int dtype, int64_t M, int C, int cstride, float* db, void* stream);

@@ -42,6 +42,8 @@ static uint32_t flags_from_env() {
     if (on("SA_NO_CELLS256")) f |= SA_DBG_NO_CELLS256;
     if (on("SA_NO_CLASS_LAUNCH")) f |= SA_DBG_NO_CLASS_LAUNCH;
     if (on("SA_GENERIC_EPILOGUE")) f |= SA_DBG_GENERIC_EPILOGUE;
+    if (on("SA_WGRAD9_LOCKSTEP")) f |= SA_DBG_WGRAD9_LOCKSTEP;
+    if (on("SA_WGRAD9_FORCE")) f |= SA_DBG_WGRAD9_FORCE;
     if (num("SA_LOCAL_ATTN_EXACT", 0) == 1) f |= SA_DBG_LOCAL_ATTN_EXACT;
     f |= ((uint32_t)num("SA_SCAN_EXACT", 0) & 7u) << SA_DBG_SCAN_EXACT_SHIFT;
     return f;

@@ -78,8 +78,26 @@ def main():
         if timing:
             torch.cuda.synchronize()
             lib.sa_debug_timing(None, 1)
+        timing9 = name == "wgrad3" and hasattr(lib, "sa_debug_timing_wgrad9")
+        if timing9:
+            torch.cuda.synchronize()
+            lib.sa_debug_timing_wgrad9(None, 1)
         t = timeit(fn, a.iters)
         print(f"{name:10s} {t * 1e3:9.1f} us  {fl / t / 1e9:8.1f} TFLOP/s   [{_ffi.lib().sa_last_conv_kernel().decode()}]", flush=True)
+        if timing9:
+            # phase stamps of the nine-tap weight gradient (-DSA_TIMING): one row of 16 sums per block, waves 0 and 4 (the two waves of SIMD 0)
+            rows, slots = 4096, ["issue", "colsum", "reads", "mfma", "dma_wait", "barrier", "prologue", "epilogue"]
+            buf9 = (ctypes.c_ulonglong * (rows * 16))()
+            lib.sa_debug_timing_wgrad9(buf9, 1)
+            v = torch.tensor(list(buf9), dtype=torch.float64).view(rows, 16)
+            ran = v.sum(dim=1) > 0
+            nb, launches = int(ran.sum()), a.iters + 1
+            body = "lock-step" if os.environ.get("SA_WGRAD9_LOCKSTEP") else "default"
+            print(f"    wgrad9 phase stamps, {body} body: {nb} blocks x {launches} launches, s_memtime ticks per block and launch (share of the wave's total)")
+            for wv, off in ((0, 0), (4, 8)):
+                s = v[ran][:, off:off + 8].sum(dim=0) / max(1, nb) / launches
+                tot = float(s.sum())
+                print(f"    wave {wv}: " + "  ".join(f"{n}={float(s[i]):.0f} ({float(s[i]) / max(tot, 1.0):.3f})" for i, n in enumerate(slots)) + f"  total={tot:.0f}")
         if timing:
             buf = (ctypes.c_ulonglong * 8)()
             lib.sa_debug_timing(buf, 1)
