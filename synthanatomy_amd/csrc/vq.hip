@@ -432,14 +432,14 @@ extern "C" int sa_vq_assign(const float* rows, const float* codebook, int64_t M,
     const size_t lds = (size_t)(5 * 16 * (D + 4) + 16 + 64 + 64 + 16 + 4) * 4;
     if (lds > 160 * 1024) return SA_EUNSUPPORTED;
     const unsigned nblk = (unsigned)((M + 15) / 16);
-    // NV = float4 pieces of a [16 codes][D] tile per lane (two tiles ahead in registers): D <= 16 / 32 / 64 / 128 / 256 / 496
+    // NV = float4 pieces of a [16 codes][D] tile per lane (two tiles ahead in registers): D <= 16 / 32 / 64 / 128 / 256 / 504
 #define SA_VQ_LAUNCH(NV) SA_LAUNCH(vq_assign_kernel<NV>, dim3(nblk), dim3(256), lds, st, rows, codebook, M, K, D, idx, zq_st, (bf16_t*)zq_lp, counts, dw, sqerr, wnorm)
     if (D <= 16) SA_VQ_LAUNCH(1);
     else if (D <= 32) SA_VQ_LAUNCH(2);
     else if (D <= 64) SA_VQ_LAUNCH(4);
     else if (D <= 128) SA_VQ_LAUNCH(8);
     else if (D <= 256) SA_VQ_LAUNCH(16);
-    else SA_VQ_LAUNCH(32);      // (D <= 496: wider rows do not fit the 160 KiB of LDS, checked above)
+    else SA_VQ_LAUNCH(32);      // (D <= 504, 163 216 bytes: wider rows do not fit the 160 KiB of LDS, checked above)
 #undef SA_VQ_LAUNCH
     SA_CHECK_LAUNCH();
     return 0;
