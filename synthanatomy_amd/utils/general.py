@@ -232,12 +232,18 @@ def shard_for_rank(n: int, rank: int, world: int, epoch: int = 0, seed: int = 0,
     return idx[rank::world]
 
 
-def save_npy(array, output_dir: str, filename: str, postfix: str, dtype=np.uint16):
-    """``<output_dir>/<name>/<name>_<postfix>.npy`` (MONAI create_file_basename layout used by NpySaver)."""
-    name = os.path.basename(filename)
+def stem(path: str) -> str:
+    """The subject's name: the file name without ``.nii.gz`` / ``.nii`` / ``.npy`` (outputs, healing files and label volumes are matched by it)."""
+    name = os.path.basename(path)
     for ext in (".nii.gz", ".nii", ".npy"):
         if name.endswith(ext):
             name = name[: -len(ext)]
+    return name
+
+
+def save_npy(array, output_dir: str, filename: str, postfix: str, dtype=np.uint16):
+    """``<output_dir>/<name>/<name>_<postfix>.npy`` (MONAI create_file_basename layout used by NpySaver)."""
+    name = stem(filename)
     d = os.path.join(output_dir, name)
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, f"{name}_{postfix}.npy")

@@ -11,6 +11,7 @@ import torch
 import anomaly_bounds
 import anomaly_ref
 import run_vqvae as RV
+from synthanatomy_amd.engines import anomaly as AS
 from synthanatomy_amd.metrics import anomaly as A
 
 
@@ -159,34 +160,34 @@ def test_healing_outputs_are_matched_by_stem(tmp_path):
     for stem in ("s0", "s1", "s10"):
         RT.save_healing(grid, grid, grid, out, f"/codes/{stem}_quantization_0.npy")
     subjects = ["/data/s0.nii.gz", "/data/s1.npy", "/data/s10.nii"]
-    recs = RV.find_healing_outputs(subjects, out)
+    recs = AS.find_healing_outputs(subjects, out)
     assert [os.path.relpath(r["healed"], out) for r in recs] == [f"{s}_quantization_0/{s}_quantization_0_healed_sample.npy" for s in ("s0", "s1", "s10")]
     assert all(r["resampled"].endswith("_quantization_0_resampled.npy") and r["nll"].endswith("_quantization_0_nll.npy") for r in recs)
-    assert RV.find_healing_outputs(subjects, out + "*/*.npy") == recs      # a glob
+    assert AS.find_healing_outputs(subjects, out + "*/*.npy") == recs      # a glob
     with pytest.raises(ValueError, match=r"s2\.npy.*s2_quantization_0_healed_sample\.npy"):
-        RV.find_healing_outputs(subjects + ["/data/s2.npy"], out)
+        AS.find_healing_outputs(subjects + ["/data/s2.npy"], out)
     # a second copy elsewhere under the directory: ambiguous
     RT.save_healing(grid, grid, grid, out + "again/", "/codes/s1_quantization_0.npy")
     with pytest.raises(ValueError, match=r"/data/s1\.npy: 2 healing outputs"):
-        RV.find_healing_outputs(subjects, out)
-    assert len(RV.find_healing_outputs(subjects, out + "s*_quantization_0")) == 3      # narrowed again
+        AS.find_healing_outputs(subjects, out)
+    assert len(AS.find_healing_outputs(subjects, out + "s*_quantization_0")) == 3      # narrowed again
     os.remove(recs[0]["nll"])
     with pytest.raises(ValueError, match=r"s0\.nii\.gz.*s0_quantization_0_nll\.npy"):
-        RV.find_healing_outputs(subjects[:1], out + "s*_quantization_0", weight="nll")
-    assert RV.find_healing_outputs(subjects[:1], out + "s*_quantization_0", weight="mask")[0] == recs[0]
-    assert RV.find_healing_outputs(subjects[:1], out + "s*_quantization_0", weight="none")[0] == recs[0]
+        AS.find_healing_outputs(subjects[:1], out + "s*_quantization_0", weight="nll")
+    assert AS.find_healing_outputs(subjects[:1], out + "s*_quantization_0", weight="mask")[0] == recs[0]
+    assert AS.find_healing_outputs(subjects[:1], out + "s*_quantization_0", weight="none")[0] == recs[0]
 
 
 def test_labels_are_matched_by_stem(tmp_path):
     for name in ("s0.npy", "s1.nii.gz", "s10.npy"):
         (tmp_path / name).write_bytes(b"")
     subjects = ["/data/s1.npy", "/data/s0.nii"]
-    assert RV.match_labels(subjects, str(tmp_path)) == [str(tmp_path / "s1.nii.gz"), str(tmp_path / "s0.npy")]
+    assert AS.match_labels(subjects, str(tmp_path)) == [str(tmp_path / "s1.nii.gz"), str(tmp_path / "s0.npy")]
     with pytest.raises(ValueError, match=r"/data/s2\.npy: 0 label volumes"):
-        RV.match_labels(["/data/s2.npy"], str(tmp_path))
+        AS.match_labels(["/data/s2.npy"], str(tmp_path))
     (tmp_path / "s0.nii").write_bytes(b"")
     with pytest.raises(ValueError, match=r"/data/s0\.nii: 2 label volumes"):
-        RV.match_labels(subjects, str(tmp_path))
+        AS.match_labels(subjects, str(tmp_path))
 
 
 class _DeviceTouched(Exception):
@@ -220,11 +221,11 @@ def test_the_new_flags_their_defaults_and_a_full_command_line(tmp_path):
             cfg["anomaly_hist_max"], cfg["anomaly_labels"], cfg["output_ext"]) == ("anomaly", "/h/outputs", "nll", 2.5, "positive", 0.125, 0.5,
                                                                                    "/labels/*.nii.gz", ".nii.gz")
     RV._check_output_flags(cfg)
-    RV._check_anomaly_flags(cfg)
+    AS._check_anomaly_flags(cfg)
     # None: half the down-sampling factor of the network the flags describe
-    assert RV._anomaly_sigma(parse_flags(_argv(tmp_path), D)) == 4.0
-    assert RV._anomaly_sigma(parse_flags(_argv(tmp_path, "--no_levels=2", "--downsample_parameters=((4,2,1,1),(4,2,1,1))"), D)) == 2.0
-    assert RV._anomaly_sigma(cfg) == 2.5
+    assert AS._anomaly_sigma(parse_flags(_argv(tmp_path), D)) == 4.0
+    assert AS._anomaly_sigma(parse_flags(_argv(tmp_path, "--no_levels=2", "--downsample_parameters=((4,2,1,1),(4,2,1,1))"), D)) == 2.0
+    assert AS._anomaly_sigma(cfg) == 2.5
 
 
 @pytest.mark.parametrize("flag, value", [("anomaly_weight", "both"), ("anomaly_weight", "None"), ("anomaly_sigma", "-1"), ("anomaly_sigma", "8.5"),

@@ -12,6 +12,7 @@ import torch
 
 import anomaly_ensemble_ref as ER
 import run_vqvae as RV
+from synthanatomy_amd.engines import anomaly as AS
 from conftest import ROOT
 from synthanatomy_amd.metrics import anomaly as A
 
@@ -128,15 +129,15 @@ def _argv(tmp_path, *extra, mode="anomaly"):
 
 def test_the_flag_its_default_and_its_two_spellings(tmp_path):
     from synthanatomy_amd.utils.general import parse_flags
-    assert RV.DEFAULTS["anomaly_ensemble"] is None and RV._ensemble_specs(parse_flags(_argv(tmp_path), RV.DEFAULTS)) is None
+    assert RV.DEFAULTS["anomaly_ensemble"] is None and AS._ensemble_specs(parse_flags(_argv(tmp_path), RV.DEFAULTS)) is None
     assert (RV.DEFAULTS["anomaly_codes"], RV.DEFAULTS["anomaly_weight"], RV.DEFAULTS["mode"]) == (None, "mask", "training")      # nothing else moved
     cfg = parse_flags(_argv(tmp_path, "--anomaly_ensemble=/h/a,/h/b/*,/h/c"), RV.DEFAULTS)
-    assert cfg["anomaly_ensemble"] == "/h/a,/h/b/*,/h/c" and RV._ensemble_specs(cfg) == ["/h/a", "/h/b/*", "/h/c"]
-    RV._check_anomaly_flags(cfg)
+    assert cfg["anomaly_ensemble"] == "/h/a,/h/b/*,/h/c" and AS._ensemble_specs(cfg) == ["/h/a", "/h/b/*", "/h/c"]
+    AS._check_anomaly_flags(cfg)
     cfg = parse_flags(_argv(tmp_path, "--anomaly_ensemble=('/h/a','/h/b')"), RV.DEFAULTS)
-    assert RV._ensemble_specs(cfg) == ["/h/a", "/h/b"]
-    RV._check_anomaly_flags(cfg)
-    RV._check_anomaly_flags(dict(cfg, anomaly_ensemble=[f"/h/{k}" for k in range(16)]))
+    assert AS._ensemble_specs(cfg) == ["/h/a", "/h/b"]
+    AS._check_anomaly_flags(cfg)
+    AS._check_anomaly_flags(dict(cfg, anomaly_ensemble=[f"/h/{k}" for k in range(16)]))
 
 
 @pytest.mark.parametrize("value, what", [("/h/a", "1 members"), (",".join(f"/h/{k}" for k in range(17)), "17 members"), ("/h/a,,/h/b", "empty spec"),
@@ -168,27 +169,27 @@ def test_healing_outputs_are_found_per_member(tmp_path):
         for stem in ("s0", "s1"):
             RT.save_healing(grid, grid, grid, d, f"/codes/{stem}_quantization_0.npy")
     subjects = ["/data/s0.nii.gz", "/data/s1.npy"]
-    members = RV.find_ensemble_outputs(subjects, dirs)
+    members = AS.find_ensemble_outputs(subjects, dirs)
     assert len(members) == 3 and all(len(recs) == 2 for recs in members)
     for d, recs in zip(dirs, members):
-        assert recs == RV.find_healing_outputs(subjects, d)
+        assert recs == AS.find_healing_outputs(subjects, d)
         assert [os.path.relpath(r["healed"], d) for r in recs] == [f"{s}_quantization_0/{s}_quantization_0_healed_sample.npy" for s in ("s0", "s1")]
     # every member needs exactly one match per subject, as a single healing does
     with pytest.raises(ValueError, match=r"s2\.npy: no healing output"):
-        RV.find_ensemble_outputs(subjects + ["/data/s2.npy"], dirs)
+        AS.find_ensemble_outputs(subjects + ["/data/s2.npy"], dirs)
     os.remove(members[1][0]["nll"])
     with pytest.raises(ValueError, match=r"s0\.nii\.gz.*s0_quantization_0_nll\.npy"):
-        RV.find_ensemble_outputs(subjects, dirs, weight="nll")
+        AS.find_ensemble_outputs(subjects, dirs, weight="nll")
     # two specs that differ as strings and reach the same healed file for s1
     with pytest.raises(ValueError, match=r"/data/s0\.nii\.gz: members 0 \(.*a/\) and 2 \(.*a/s\*\) .* same healed file"):
-        RV.find_ensemble_outputs(subjects, [dirs[0], dirs[1], dirs[0] + "s*"])
+        AS.find_ensemble_outputs(subjects, [dirs[0], dirs[1], dirs[0] + "s*"])
     os.symlink(dirs[0], str(tmp_path / "link"))
     with pytest.raises(ValueError, match=r"same healed file"):
-        RV.find_ensemble_outputs(subjects, [dirs[0], str(tmp_path / "link") + "/"])
+        AS.find_ensemble_outputs(subjects, [dirs[0], str(tmp_path / "link") + "/"])
     # a member whose code grid has another shape
     RT.save_healing(np.zeros((2, 2, 3)), np.zeros((2, 2, 3)), np.zeros((2, 2, 3)), dirs[2], "/codes/s1_quantization_0.npy")
     with pytest.raises(ValueError, match=r"/data/s1\.npy: member 2 \(.*c/\) .* shape \(2, 2, 3\), member 0 \(.*a/\) has \(2, 2, 2\)"):
-        RV.find_ensemble_outputs(subjects, dirs)
+        AS.find_ensemble_outputs(subjects, dirs)
 
 
 def test_compose_fp32_of_one_member_is_the_identity_and_the_scale_is_the_hosts():

@@ -11,6 +11,7 @@ import torch
 
 import components_ref as ref
 import run_vqvae as RV
+from synthanatomy_amd.engines import anomaly as AS
 from synthanatomy_amd.metrics import components as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -185,7 +186,7 @@ def test_the_flags_their_defaults_and_a_full_command_line(tmp_path, no_device):
     assert (D["anomaly_min_component"], D["anomaly_connectivity"]) == (None, 26)
     cfg = parse_flags(_argv(tmp_path, "--anomaly_threshold=0.125", "--anomaly_min_component=20", "--anomaly_connectivity=18"), D)
     assert (cfg["anomaly_min_component"], cfg["anomaly_connectivity"]) == (20, 18)
-    RV._check_anomaly_flags(cfg)
+    AS._check_anomaly_flags(cfg)
     for extra in (("--anomaly_threshold=0.1", "--anomaly_min_component=1"), ("--anomaly_threshold=0.1", "--anomaly_connectivity=6"),
                   ("--anomaly_threshold=0.1", "--anomaly_min_component=4", "--anomaly_connectivity=26", "--anomaly_labels=/l")):
         with pytest.raises(_DeviceTouched):

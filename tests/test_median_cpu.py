@@ -10,6 +10,7 @@ import torch
 
 import median_ref as ref
 import run_vqvae as RV
+from synthanatomy_amd.engines import anomaly as AS
 from synthanatomy_amd.metrics import median as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -220,7 +221,7 @@ def test_the_flags_their_defaults_and_a_full_command_line(tmp_path, no_device):
     assert (D["anomaly_median"], D["anomaly_mask"], D["anomaly_mask_threshold"], D["anomaly_mask_erosion"]) == (None, None, 0.0, 0)
     cfg = parse_flags(_argv(tmp_path, "--anomaly_median=3", "--anomaly_mask=scan", "--anomaly_mask_threshold=0.125", "--anomaly_mask_erosion=2"), D)
     assert (cfg["anomaly_median"], cfg["anomaly_mask"], cfg["anomaly_mask_threshold"], cfg["anomaly_mask_erosion"]) == (3, "scan", 0.125, 2)
-    RV._check_anomaly_flags(cfg)
+    AS._check_anomaly_flags(cfg)
     for extra in (("--anomaly_median=5",), ("--anomaly_mask=scan",), ("--anomaly_mask=/masks", "--anomaly_mask_erosion=4"), ("--anomaly_median=1",),
                   ("--anomaly_mask=scan", "--anomaly_mask_threshold=-1", "--anomaly_median=3", "--anomaly_threshold=0.1", "--anomaly_min_component=2")):
         with pytest.raises(_DeviceTouched):
